@@ -1,6 +1,14 @@
 """GICP iterations/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n POINTS] [--dim 3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n POINTS] [--dim 3] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets the clouds up, warms up, times the K
+iterations, writes their outputs when --dump-outputs is given, and prints the result line.  --full adds
+everything else the line can carry, each from runs of its own after the timed one: the warm-start
+repeat, the per-launch k_corr timing runs (roofline, passes, valu), the profiled traffic and the CPU
+baseline.  --dump-outputs DIR writes what the timed registration returned to its caller (Engine.align's
+pose and the deterministic fields of its result) as DIR/transform.npy and DIR/result.npy (float64); the
+clouds are seeded, so two builds given the same arguments register identical inputs.
 
 A step is one outer GICP iteration (gicp.py:116-167): correspondences + weights +
 statistics on the GPU (k_corr, reduced inside the launch), the RCCL all-reduce of the
@@ -64,7 +72,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--n", "--points", dest="n", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the warm-start repeat, the k_corr "
+                         "timing runs (roofline, passes, valu), the profiled traffic and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed registration returned (transform.npy, result.npy) into DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline")
     ap.add_argument("--cpu-workers", type=int, default=16,
                     help="cKDTree workers of the CPU baseline (the GPU box's CPU share is 16)")
     ap.add_argument("--warm", action="store_true",
@@ -209,6 +222,67 @@ def setup_exchange(eng, gd, rank, world, exchange, share_gpu):
     return peer_note, comm_ranks, comm_kind
 
 
+RESULT_FIELDS = ("iterations", "correspondences", "final_loss", "mse")   # rows of result.npy
+
+
+def dump_outputs(out_dir, T, res):
+    """--dump-outputs: what the timed Engine.align returned to its caller, as float64 .npy files -- the
+    final pose (transform.npy, (dim+1) x (dim+1)) and the fields of its result that do not depend on
+    the clock (result.npy, in RESULT_FIELDS order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "transform.npy"), np.asarray(T, dtype=np.float64))
+    np.save(os.path.join(out_dir, "result.npy"), np.array([res[k] for k in RESULT_FIELDS], dtype=np.float64))
+
+
+def full_fields(a, world, name, res, comm_kind, corr_ms_total, per_iter, warm_elapsed):
+    """What --full adds to the line: the k_corr roofline and per-pass times from the kernel timing runs,
+    the profiled traffic, the warm-start repeat and the VALU rate of the screen."""
+    n_shard = a.n / max(world, a.shard_sim)
+    corr_avg_ms = corr_ms_total / a.steps
+    alg_bytes = bytes_per_point(a.dim) * (n_shard + a.n)
+    impl_bytes = IMPL_BYTES_PER_POINT * (n_shard + a.n)
+    achieved = alg_bytes / (corr_avg_ms * 1e-3) / 1e9
+    n_mov = min(10, a.steps)
+    pairs = res["pairs_total"] / a.steps / world   # mean per launch (summed over ranks by the all-reduce)
+    traffic, traffic_src, traffic_pp, traffic_note = (measured_traffic(name, a.steps, a.warmup) if world == 1 and
+                                                      a.shard_sim <= 1 and not a.warm else
+                                                      (None, None, None, "not profiled (multi-rank or diagnostic run)"))
+    return {
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                     "traffic_note": traffic_note,
+                     "traffic_per_pass": None if not traffic_pp else
+                     {k: traffic_pp.get(k) for k in ("first_pass", "moving_mean", "converged_mean", "timed_mean")},
+                     "traffic_vs_alg": None if not traffic_pp else
+                     {k: round(traffic_pp[k] / alg_bytes, 2) for k in ("first_pass", "moving_mean", "converged_mean")
+                      if traffic_pp.get(k)},
+                     "kernel": "k_corr", "kernel_avg_ms": corr_avg_ms, "alg_bytes_per_launch": alg_bytes,
+                     "alg_bytes_rule": f"SURVEY.md 8(d): {bytes_per_point(a.dim)} B x (N/G + M)",
+                     "impl_bytes_per_launch": impl_bytes,
+                     "impl_frac": impl_bytes / (corr_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                     "kernel_timing": "HIP events, every k_corr launch of K timed once (8 identical cold-start "
+                                      "K-iteration runs at sampling offsets 0..7, stride 8)",
+                     "kernel_note": ("the inner solve is k_solve after the RCCL all-reduce (not in k_corr's time)"
+                                     if comm_kind == "rccl" else
+                                     "k_corr's final workgroup also runs the one-wave inner solve and pose update "
+                                     "(~5 us, inside the timed duration)" +
+                                     (", after the in-kernel peer exchange" if comm_kind == "peer" else ""))},
+        "passes": {"moving_pass_us": float(np.mean(per_iter[1:1 + n_mov])) * 1e3,
+                   "passes_0_9_us": float(np.mean(per_iter[:n_mov])) * 1e3,
+                   "converged_pass_us": float(np.mean(per_iter[-n_mov:])) * 1e3,
+                   "first_pass_us": float(per_iter[0]) * 1e3,
+                   "k_corr_us_per_iteration": [round(float(x) * 1e3, 1) for x in per_iter],
+                   "note": "moving = mean k_corr of iterations 1-10 (the pose still moves; rounds 1-3 reported "
+                           "iterations 0-9 under this name, now passes_0_9_us), converged = last 10"},
+        "warm_start": None if warm_elapsed is None else
+        {"value": a.steps / warm_elapsed, "ms_per_step": warm_elapsed * 1e3 / a.steps,
+         "note": "diagnostic, not the metric: the same K iterations again, continuing from the caches"},
+        "valu": {"pairs_per_launch": pairs, "tflops": pairs * FLOP_PER_PAIR / (corr_avg_ms * 1e-3) / 1e12,
+                 "peak_tflops": FP32_PEAK_TFLOPS,
+                 "frac": pairs * FLOP_PER_PAIR / (corr_avg_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS},
+    }
+
+
 def main():
     a = parse()
     if a.gpus < 1:
@@ -271,22 +345,24 @@ def main():
     T, res = eng.align(None, params)
     sync()
     elapsed = time.perf_counter() - t1
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, T, res)
     warm_elapsed = None
-    if not a.warm:   # diagnostic: the same registration again, continuing from the caches it left
+    if a.full and not a.warm:   # diagnostic: the same registration again, continuing from the caches it left
         sync()
         t2 = time.perf_counter()
         eng.align(None, params)
         sync()
         warm_elapsed = time.perf_counter() - t2
     params.timing_stride = 0
-    # kernel timing runs (not the metric): an event pair around every launch adds queue work, so each
-    # run samples every 8th k_corr launch, and the launch cost falls ~4x as the pose converges, so one
+    # kernel timing runs (--full, not the metric): an event pair around every launch adds queue work, so
+    # each run samples every 8th k_corr launch, and the launch cost falls ~4x as the pose converges, so one
     # sample set is biased; 8 identical K-iteration runs with the sampling offset 0..7 time every
     # launch once
     corr_ms_total = 0.0
     timed = 0
-    per_iter = np.full(a.steps, np.nan)
-    for off in range(8):
+    per_iter = np.full(a.steps if a.full else 0, np.nan)
+    for off in range(8 if a.full else 0):
         params.timing_offset = off
         if not a.warm:
             eng.reset_cache()   # every timing run starts cold, as the timed run did
@@ -297,7 +373,7 @@ def main():
         got = ~np.isnan(t_it)
         per_iter[:len(t_it)][got] = t_it[got]
     params.timing_offset = 0
-    assert timed == a.steps, (timed, a.steps)
+    assert timed == (a.steps if a.full else 0), (timed, a.steps)
     if dist is not None:
         import torch
         t = torch.tensor([elapsed, corr_ms_total, warm_elapsed or 0.0, *per_iter], dtype=torch.float64,
@@ -314,16 +390,6 @@ def main():
         return
     from gicp.synthetic import rotation_angle_error, translation_error
     rot_err, tr_err = rotation_angle_error(T, Tgt), translation_error(T, Tgt)
-    n_shard = a.n / max(world, a.shard_sim)
-    corr_avg_ms = corr_ms_total / a.steps
-    alg_bytes = bytes_per_point(a.dim) * (n_shard + a.n)
-    impl_bytes = IMPL_BYTES_PER_POINT * (n_shard + a.n)
-    achieved = alg_bytes / (corr_avg_ms * 1e-3) / 1e9
-    n_mov = min(10, a.steps)
-    pairs = res["pairs_total"] / a.steps / world   # mean per launch (summed over ranks by the all-reduce)
-    traffic, traffic_src, traffic_pp, traffic_note = (measured_traffic(name, a.steps, a.warmup) if world == 1 and
-                                                      a.shard_sim <= 1 and not a.warm else
-                                                      (None, None, None, "not profiled (multi-rank or diagnostic run)"))
     line = {
         "metric": "GICP iterations/sec (and ms/iter) at N points, 1/2/4/8 GPU; final transform error",
         "value": a.steps / elapsed,
@@ -351,44 +417,15 @@ def main():
         {"mean": res["exchange_us_mean"], "min": res["exchange_us_min"],
          "note": "rank 0's final workgroup per launch of the timed call: its stores into every rank's area until "
                  "every rank's flag arrived (includes waiting for the slower rank)"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                     "traffic_note": traffic_note,
-                     "traffic_per_pass": None if not traffic_pp else
-                     {k: traffic_pp.get(k) for k in ("first_pass", "moving_mean", "converged_mean", "timed_mean")},
-                     "traffic_vs_alg": None if not traffic_pp else
-                     {k: round(traffic_pp[k] / alg_bytes, 2) for k in ("first_pass", "moving_mean", "converged_mean")
-                      if traffic_pp.get(k)},
-                     "kernel": "k_corr", "kernel_avg_ms": corr_avg_ms, "alg_bytes_per_launch": alg_bytes,
-                     "alg_bytes_rule": f"SURVEY.md 8(d): {bytes_per_point(a.dim)} B x (N/G + M)",
-                     "impl_bytes_per_launch": impl_bytes,
-                     "impl_frac": impl_bytes / (corr_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "kernel_timing": "HIP events, every k_corr launch of K timed once (8 identical cold-start "
-                                      "K-iteration runs at sampling offsets 0..7, stride 8)",
-                     "kernel_note": ("the inner solve is k_solve after the RCCL all-reduce (not in k_corr's time)"
-                                     if comm_kind == "rccl" else
-                                     "k_corr's final workgroup also runs the one-wave inner solve and pose update "
-                                     "(~5 us, inside the timed duration)" +
-                                     (", after the in-kernel peer exchange" if comm_kind == "peer" else ""))},
-        "passes": {"moving_pass_us": float(np.mean(per_iter[1:1 + n_mov])) * 1e3,
-                   "passes_0_9_us": float(np.mean(per_iter[:n_mov])) * 1e3,
-                   "converged_pass_us": float(np.mean(per_iter[-n_mov:])) * 1e3,
-                   "first_pass_us": float(per_iter[0]) * 1e3,
-                   "k_corr_us_per_iteration": [round(float(x) * 1e3, 1) for x in per_iter],
-                   "note": "moving = mean k_corr of iterations 1-10 (the pose still moves; rounds 1-3 reported "
-                           "iterations 0-9 under this name, now passes_0_9_us), converged = last 10"},
-        "warm_start": None if warm_elapsed is None else
-        {"value": a.steps / warm_elapsed, "ms_per_step": warm_elapsed * 1e3 / a.steps,
-         "note": "diagnostic, not the metric: the same K iterations again, continuing from the caches"},
         "start": "warm (diagnostic)" if a.warm else "cold (caches reset after the warmup)",
-        "valu": {"pairs_per_launch": pairs, "tflops": pairs * FLOP_PER_PAIR / (corr_avg_ms * 1e-3) / 1e12,
-                 "peak_tflops": FP32_PEAK_TFLOPS,
-                 "frac": pairs * FLOP_PER_PAIR / (corr_avg_ms * 1e-3) / 1e12 / FP32_PEAK_TFLOPS},
         "setup_ms": setup_ms,
         "final_error": {"rot_rad": rot_err, "trans": tr_err, "vs": "ground truth after steps+0 iterations"},
         "correspondences": res["correspondences"],
         "ambiguous_last_pass": res["ambiguous"],
+        "full": a.full,
     }
+    if a.full:
+        line.update(full_fields(a, world, name, res, comm_kind, corr_ms_total, per_iter, warm_elapsed))
     if a.share_gpu:
         line["diagnostic"] = f"{world} ranks sharing GPU 0 (peer exchange protocol timing, not a multi-GPU job)"
         line["cpu_baseline"] = None
@@ -399,7 +436,7 @@ def main():
         line["cpu_baseline"] = None
         print(json.dumps(line))
         return
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         try:
             its, setup, dt = cpu_baseline(src, tgt, kw, a.cpu_workers)
             line["cpu_baseline"] = {"value": its, "unit": "it/s", "cores": a.cpu_workers, "kind": "port",

@@ -9,7 +9,7 @@ for r in $(seq 1 $REPS); do
   i=0
   for v in "$@"; do
     i=$((i+1))
-    env $v timeout -k 10 200 python bench.py --no-cpu-baseline $BENCH_ARGS > $OUT/v${i}_r$r.json 2> $OUT/v${i}_r$r.err || { echo "variant $v failed"; tail $OUT/v${i}_r$r.err; exit 1; }
+    env $v timeout -k 10 200 python bench.py --full --no-cpu-baseline $BENCH_ARGS > $OUT/v${i}_r$r.json 2> $OUT/v${i}_r$r.err || { echo "variant $v failed"; tail $OUT/v${i}_r$r.err; exit 1; }
   done
 done
 python - "$OUT" "$REPS" "$@" <<'PY'

@@ -7,7 +7,7 @@
 # Steps (ARGS after ':' are passed through; use ',' for spaces inside one step):
 #   tests[:PYTEST_ARGS]        pytest -m gpu over tests/ (or the given files / -k expression)
 #   smoke                      __graft_entry__.smoke()
-#   bench[:BENCH_ARGS]         one bench.py line -> bench_<n>.json (default: the driver's command)
+#   bench[:BENCH_ARGS]         one bench.py --full line -> bench_<n>.json (default: the driver's command)
 #   ab:REPS:BENCH_ARGS:V1|V2   interleaved A/B of bench.py variants (scripts/bench_variants.sh); each Vi is an
 #                              environment assignment list, e.g. "X=0|GICP_LIB_VARIANT=base"
 #   tail[:N,ARGS]              tail-build stage stamps of one registration (scripts/tail_run.py, GICP_TAIL build)
@@ -39,7 +39,7 @@ for step in "$@"; do
     smoke)
       timeout -k 10 $TL python3 -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1; rc=$?; tail -1 $log ;;
     bench)
-      timeout -k 10 $TL python3 bench.py ${arg:---gpus 1 --steps 20 --warmup 5} > $OUT/bench_$n.json 2> $log; rc=$?
+      timeout -k 10 $TL python3 bench.py --full ${arg:---gpus 1 --steps 20 --warmup 5} > $OUT/bench_$n.json 2> $log; rc=$?
       [ $rc = 0 ] && python3 -c "import json;d=json.load(open('$OUT/bench_$n.json'));p=d.get('passes',{});print(round(d['value'],1),d['unit'],'frac',round(d['roofline']['frac'],4),'moving',round(p.get('moving_pass_us',0),1),'conv',round(p.get('converged_pass_us',0),1));print(' '.join(f'{x:.0f}' for x in p.get('k_corr_us_per_iteration',[])))" ;;
     ab)
       reps=${arg%%:*}; rest=${arg#*:}; bargs=${rest%%:*}; vars=${rest#*:}

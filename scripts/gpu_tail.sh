@@ -5,10 +5,10 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${1:-tail}
 mkdir -p $OUT
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench20.json 2> $OUT/bench20.err || { echo bench failed; tail $OUT/bench20.err; exit 1; }
-timeout -k 10 300 python3 bench.py --n 100000 --no-cpu-baseline > $OUT/c2.json 2> $OUT/c2.err || { echo c2 failed; tail $OUT/c2.err; exit 1; }
-timeout -k 10 300 python3 bench.py --shard-sim 8 --no-cpu-baseline > $OUT/sim8.json 2> $OUT/sim8.err || { echo sim8 failed; tail $OUT/sim8.err; exit 1; }
-timeout -k 10 300 python3 bench.py --n 20000 --shard-sim 2 --steps 100 --no-cpu-baseline > $OUT/sim2_20k.json 2> $OUT/sim2_20k.err || { echo sim2 failed; tail $OUT/sim2_20k.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench20.json 2> $OUT/bench20.err || { echo bench failed; tail $OUT/bench20.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --n 100000 --no-cpu-baseline > $OUT/c2.json 2> $OUT/c2.err || { echo c2 failed; tail $OUT/c2.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --shard-sim 8 --no-cpu-baseline > $OUT/sim8.json 2> $OUT/sim8.err || { echo sim8 failed; tail $OUT/sim8.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --n 20000 --shard-sim 2 --steps 100 --no-cpu-baseline > $OUT/sim2_20k.json 2> $OUT/sim2_20k.err || { echo sim2 failed; tail $OUT/sim2_20k.err; exit 1; }
 for f in bench20 c2 sim8 sim2_20k; do python -c "import json;d=json.load(open('$OUT/$f.json'));print('$f',round(d['value'],1),d['unit'],'corr_ms',round(d['roofline']['kernel_avg_ms'],4), 'mov',round(d['passes']['moving_pass_us'],1), 'conv',round(d['passes']['converged_pass_us'],1))"; done
 fi
 [ "${SKIP_TAIL:-0}" = 1 ] && exit 0

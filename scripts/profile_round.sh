@@ -10,7 +10,7 @@ OUT=gpurun_out/${1:-prof}
 PD=${2:-profiles/r05}
 STEPS=${STEPS:-20}
 WARMUP=${WARMUP:-5}
-CMD="bench.py --gpus 1 --steps $STEPS --warmup $WARMUP"
+CMD="bench.py --gpus 1 --steps $STEPS --warmup $WARMUP --full"
 mkdir -p $OUT $PD
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t --output-format csv -- python3 $CMD > $OUT/bench_under_rocprof.json 2> $OUT/trace.err || { echo trace failed; exit 1; }
 python3 scripts/trace_iters.py $OUT/trace $STEPS > $OUT/iterations.txt

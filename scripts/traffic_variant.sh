@@ -6,7 +6,7 @@ set -o pipefail
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:?out}
 V=${2:-}
-CMD="bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline"
+CMD="bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline"
 mkdir -p $OUT
 i=2
 for set in "FETCH_SIZE GRBM_GUI_ACTIVE" "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum"; do

@@ -92,6 +92,68 @@ def test_traffic_comes_only_from_a_profile_of_the_same_command():
     assert b.measured_traffic("2d_segments_1000k", 20, 5)[0] is None
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_full_is_off_by_default(monkeypatch):
+    """A plain run measures the headline only: --full (and --dump-outputs) are opt-in."""
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = b.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_the_pose_and_result_as_float64(tmp_path):
+    import numpy as np
+    b = _bench_module()
+    T = np.arange(16, dtype=np.float64).reshape(4, 4) / 7
+    res = {"iterations": 20, "correspondences": 999_999, "final_loss": 10.5, "mse": 1.5e-3, "wall_ms": 1.0}
+    out = tmp_path / "a" / "b"   # created when missing
+    b.dump_outputs(str(out), T, res)
+    assert sorted(p.name for p in out.iterdir()) == ["result.npy", "transform.npy"]
+    t, r = np.load(out / "transform.npy"), np.load(out / "result.npy")
+    assert t.dtype == r.dtype == np.float64
+    assert np.array_equal(t, T)
+    assert b.RESULT_FIELDS == ("iterations", "correspondences", "final_loss", "mse")
+    assert np.array_equal(r, [20, 999_999, 10.5, 1.5e-3])   # no clock-dependent field
+
+
+FULL_ONLY = ("roofline", "passes", "valu", "warm_start")
+
+
+@pytest.mark.gpu
+def test_plain_and_full_runs_on_a_small_workload(tmp_path):
+    """A plain run prints the headline fields without the --full measurements and times exactly --steps
+    iterations; --full adds them; both dump the same outputs for the same (seeded) arguments."""
+    import numpy as np
+    args = ["--gpus", "1", "--n", "20000", "--steps", "3", "--warmup", "1"]
+    r = _run([*args, "--dump-outputs", str(tmp_path / "plain")])
+    assert r.returncode == 0, r.stderr
+    d = _json_line(r.stdout)
+    assert d["full"] is False and not [k for k in FULL_ONLY if k in d] and d["cpu_baseline"] is None
+    assert d["steps"] == 3 and d["unit"] == "it/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] - 1e3) < 1e-6
+    r = _run([*args, "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert r.returncode == 0, r.stderr
+    f = _json_line(r.stdout)
+    assert f["full"] is True and all(k in f for k in FULL_ONLY)
+    assert len(f["passes"]["k_corr_us_per_iteration"]) == 3 and f["roofline"]["kernel_avg_ms"] > 0
+    for name in ("transform", "result"):
+        p, q = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert p.dtype == np.float64 and np.all(np.isfinite(p))
+        # the same build on the same inputs: at most a reordered fp64 sum over 2e4 points apart (~2e4 x 2^-53)
+        assert np.allclose(p, q, rtol=1e-9, atol=1e-12)
+    assert np.load(tmp_path / "plain" / "result.npy")[0] == 3   # iterations == --steps
+
+
 class _FakeEngine:
     """The exchange surface of gicp.Engine, no GPU: peer_init fails on the ranks in `fail_on`."""
 

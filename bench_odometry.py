@@ -33,6 +33,8 @@ def main():
                     help="staged scans copied by the library before stage_target returns (the default for callers "
                          "that refill their buffer); without it the bench, which holds every frame untouched in "
                          "memory, lends them (GICP_STAGE_BORROW: no copy on the calling thread)")
+    ap.add_argument("--voxel-size", type=float, default=None,
+                    help="voxel-filter every scan on the device before it is indexed (metres; default: off)")
     a = ap.parse_args()
     from gicp import synthetic as S
     from gicp.odometry import Odometry
@@ -54,7 +56,7 @@ def main():
         # no per-launch HIP event pairs (a diagnostic the line does not report: each pair is queue work between
         # two launches); --kernel-times keeps the library default (every 8th launch timed)
         p.timing_stride = -1
-    odo = Odometry(3, params=p, borrow=not a.copy)
+    odo = Odometry(3, params=p, borrow=not a.copy, voxel_size=a.voxel_size)
     # warm-up on the first two frames (library init, allocation), then restart the stream
     odo.step(frames[0][0])
     odo.step(frames[1][0], frames[2][0])
@@ -109,6 +111,8 @@ def main():
                   "path_length": float(sum(np.linalg.norm(frames[k][1][:3, 3] - frames[k - 1][1][:3, 3])
                                            for k in range(1, len(frames))))},
     }
+    if a.voxel_size is not None:
+        line["voxel"] = {"voxel_size": a.voxel_size, "points_last_frame": odo.eng.cloud_size("target")}
     print(json.dumps(line))
 
 

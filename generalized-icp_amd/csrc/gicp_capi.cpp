@@ -43,6 +43,9 @@ hipError_t launch_graph_pack(const GraphArgs&, hipStream_t);
 hipError_t launch_rotate_cov(const double4*, const int32_t*, int64_t, int, const double*, double*, hipStream_t);
 hipError_t launch_top_weights(const double*, const int64_t*, const int32_t*, int64_t, int, double*, int64_t*, int, double*, int64_t*,
                               int64_t*, hipStream_t);
+hipError_t voxel_temp_bytes(int64_t, int, size_t*, hipStream_t);
+hipError_t launch_voxel(const VoxelArgs&, hipStream_t);
+hipError_t launch_points_out(const double*, const int32_t*, int64_t, int, double*, hipStream_t);
 int corr_grid(int q_tiles, int shard, int nshards);
 int solve_pose(int d, const double* st, const double* Tk, double* Tout, double* loss_out);
 }  // namespace gicp
@@ -266,6 +269,17 @@ struct BuildScratch {
     int cap_k_hint[4] = {0, 0, 0, 0};  // last tile extent-cap step per dimension (tiling warm start)
     double* h_pinned = nullptr;       // pinned host copy of the input (staged builds)
     size_t cap_pinned = 0;
+    // voxel filter (gicp_voxel.hip): the raw cloud, keys and indices before and after the sort, head flags,
+    // voxel ids, per-wave carries, per-voxel centroids and counts, the kept counts, rocPRIM scratch, results
+    double* v_raw = nullptr;
+    uint64_t *v_keys = nullptr, *v_keys2 = nullptr;
+    int32_t *v_idx = nullptr, *v_idx2 = nullptr, *v_flag = nullptr, *v_vid = nullptr, *v_cnt = nullptr, *v_ocnt = nullptr;
+    double *v_cfirst = nullptr, *v_clast = nullptr, *v_cent = nullptr;
+    int2* v_cmeta = nullptr;
+    unsigned char* v_tmp = nullptr;
+    unsigned long long* v_res = nullptr;
+    size_t cap_vraw = 0, cap_vkeys = 0, cap_vkeys2 = 0, cap_vidx = 0, cap_vidx2 = 0, cap_vflag = 0, cap_vvid = 0, cap_vcnt = 0,
+           cap_vocnt = 0, cap_vcf = 0, cap_vcl = 0, cap_vcent = 0, cap_vcm = 0, cap_vtmp = 0;
     std::unique_ptr<WorkerPool> pool;  // tiling threads (lazily started)
     WorkerPool& workers() {
         if (!pool) {
@@ -285,8 +299,25 @@ struct BuildScratch {
         dfree(d_amb);
         if (h_pinned) quiet(hipHostFree(h_pinned));
         h_pinned = nullptr;
+        dfree(v_raw);
+        dfree(v_keys);
+        dfree(v_keys2);
+        dfree(v_idx);
+        dfree(v_idx2);
+        dfree(v_flag);
+        dfree(v_vid);
+        dfree(v_cnt);
+        dfree(v_ocnt);
+        dfree(v_cfirst);
+        dfree(v_clast);
+        dfree(v_cent);
+        dfree(v_cmeta);
+        dfree(v_tmp);
+        dfree(v_res);
         pool.reset();
         cap_in = cap_codes = cap_codes2 = cap_idx = cap_sort = cap_gnb = cap_gnbh = cap_pinned = 0;
+        cap_vraw = cap_vkeys = cap_vkeys2 = cap_vidx = cap_vidx2 = cap_vflag = cap_vvid = cap_vcnt = cap_vocnt = 0;
+        cap_vcf = cap_vcl = cap_vcent = cap_vcm = cap_vtmp = 0;
     }
 };
 
@@ -346,6 +377,9 @@ struct gicp_ctx {
     // cloud-build scratch (synchronous builds) and per-source-tile arrays, grow-only (a frame stream
     // allocates once)
     BuildScratch bs;
+    // voxel filter of every later cloud build (gicp_set_voxel): leaf 0 = off
+    double voxel_leaf = 0.0;
+    int voxel_min = 1;
     // staged targets (gicp_stage_target / gicp_commit_target): a ring of GICP_MAX_STAGED slots, each
     // built into its own cloud on its own stream by a host thread while the current target is
     // registered; commits take them in staging order
@@ -366,6 +400,8 @@ struct gicp_ctx {
         int dim = 0;
         bool graph = false;
         int device = 0;
+        double voxel_leaf = 0.0;       // the context's filter setting when the build was staged
+        int voxel_min = 1;
         gicp_params p{};
         int rc = GICP_OK;
         std::string err;
@@ -607,34 +643,9 @@ int shard_tile_count(int ntiles, int shard, int nshards) {
     return mine;
 }
 
-// cov_shard / cov_nshards: the covariances are computed for that shard's tiles only (a sharded source: every
-// rank needs the whole cloud's index for the neighbourhoods, but only its own tiles' covariances); the other
-// rows read NaN.
-// tile_points: points per tile at most (64; a source may take 32 or 16: GICP_SRC_TILE, DESIGN.md §5)
-void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_params& p, bool graph,
-                 BuildScratch& bs, hipStream_t st, bool staged = false, int cov_shard = 0, int cov_nshards = 1,
-                 int tile_points = kTile) {
-    if (!xyz || n <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
-    if (n > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cloud too large (> 2^31 points)"};
-    const bool verbose = std::getenv("GICP_VERBOSE") && std::getenv("GICP_VERBOSE")[0] == '1';
-    auto tprev = std::chrono::steady_clock::now();
-    std::string tlog;
-    auto tick = [&](const char* what) {
-        if (!verbose) return;
-        HIPCHK(hipStreamSynchronize(st));
-        const auto t = std::chrono::steady_clock::now();
-        char b[64];
-        std::snprintf(b, sizeof b, " %s %.1f", what, std::chrono::duration<double, std::milli>(t - tprev).count());
-        tlog += b;
-        tprev = t;
-    };
-    cl.n = 0;   // buffers are kept (grow-only) and reused
-    cl.cov_ready = false;
-    cl.graph_ready = false;
-    cl.dim = dim;
-    cl.bits = dim == 3 ? 10 : 16;
-    // one fused, branch-free pass: bounds and the finiteness test (v - v is NaN for NaN and +-inf)
-    double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+// Bounds of a host cloud and its finiteness test in one fused, branch-free pass (v - v is NaN for NaN and +-inf).
+void scan_bounds(const double* xyz, int64_t n, int dim, double (&mn)[3], double (&mx)[3]) {
+    for (int a = 0; a < 3; ++a) mn[a] = mx[a] = 0.0;
     bool finite = true;
     auto scan = [&](auto D_) {
         constexpr int D = decltype(D_)::value;
@@ -655,16 +666,170 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
     if (dim == 3) scan(std::integral_constant<int, 3>{});
     else scan(std::integral_constant<int, 2>{});
     if (!finite) throw Fail{GICP_E_INVALID, "cloud contains non-finite coordinates"};
+}
+
+// doubles from the ordered-integer form gicp_voxel.hip reduces min / max in
+double dec_ordered(unsigned long long e) {
+    const unsigned long long b = (e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
+    double v;
+    std::memcpy(&v, &b, sizeof v);
+    return v;
+}
+
+struct VoxelOut {
+    int64_t M = 0;                  // voxels kept
+    double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};   // bounds of their centroids
+};
+
+// The voxel filter (gicp_voxel.hip) of the device cloud d_raw [n][dim] with host bounds mn / mx:
+// centroids of the voxels holding >= min_points points into d_out [M][dim] in key order, their counts into
+// bs.v_ocnt.  One stream sync; the result words (centroid bounds, M) are all that returns to the host.
+VoxelOut voxel_filter(BuildScratch& bs, const double* d_raw, int64_t n, int dim, const double (&mn)[3],
+                      const double (&mx)[3], double leaf, int min_points, double* d_out, hipStream_t st) {
+    VoxelArgs va{};
+    va.raw = d_raw;
+    va.n = n;
+    va.dim = dim;
+    va.min_points = min_points;
+    va.leaf = leaf;
+    // the lowest cell per axis and the key bits: division by a positive leaf is monotone, so every point's
+    // cell lies in [floor(min / leaf), floor(max / leaf)], computed here as the device computes it
+    const double lim = dim == 3 ? 2097152.0 : 2147483648.0;   // 2^21, 2^31 cells per axis
+    int total = 0;
+    for (int a = 0; a < dim; ++a) {
+        const double c0 = std::floor(mn[a] / leaf), c1 = std::floor(mx[a] / leaf);
+        const double range = c1 - c0 + 1.0;
+        if (!(std::fabs(c0) < 4503599627370496.0 && std::fabs(c1) < 4503599627370496.0 && range <= lim)) {
+            char b[160];
+            std::snprintf(b, sizeof b, "voxel grid too wide: axis %d spans %.6g cells of leaf %g (at most 2^%d per axis in %d-D)",
+                          a, range, leaf, dim == 3 ? 21 : 31, dim);
+            throw Fail{GICP_E_INVALID, b};
+        }
+        va.cmin[a] = c0;
+        uint64_t r = (uint64_t)range - 1;
+        int bits = 0;
+        while (r) ++bits, r >>= 1;
+        va.bits[a] = bits;
+        total += bits;
+    }
+    va.end_bit = std::max(1, total);
+    const size_t nw = (size_t)((n + kWave - 1) / kWave);
+    dreserve(bs.v_keys, bs.cap_vkeys, (size_t)n);
+    dreserve(bs.v_keys2, bs.cap_vkeys2, (size_t)n);
+    dreserve(bs.v_idx, bs.cap_vidx, (size_t)n);
+    dreserve(bs.v_idx2, bs.cap_vidx2, (size_t)n);
+    dreserve(bs.v_flag, bs.cap_vflag, (size_t)n);
+    dreserve(bs.v_vid, bs.cap_vvid, (size_t)n);
+    dreserve(bs.v_cnt, bs.cap_vcnt, (size_t)n);
+    dreserve(bs.v_ocnt, bs.cap_vocnt, (size_t)n);
+    dreserve(bs.v_cent, bs.cap_vcent, (size_t)n * 3);
+    dreserve(bs.v_cfirst, bs.cap_vcf, nw * 4);
+    dreserve(bs.v_clast, bs.cap_vcl, nw * 4);
+    dreserve(bs.v_cmeta, bs.cap_vcm, nw);
+    if (!bs.v_res) dalloc(bs.v_res, (size_t)kVoxelRes);
+    size_t tmp_bytes = 0;
+    HIPCHK(voxel_temp_bytes(n, va.end_bit, &tmp_bytes, st));
+    dreserve(bs.v_tmp, bs.cap_vtmp, tmp_bytes + 16);
+    va.keys = bs.v_keys;
+    va.keys_s = bs.v_keys2;
+    va.idx = bs.v_idx;
+    va.idx_s = bs.v_idx2;
+    va.flag = bs.v_flag;
+    va.vid1 = bs.v_vid;
+    va.cfirst = bs.v_cfirst;
+    va.clast = bs.v_clast;
+    va.cmeta = bs.v_cmeta;
+    va.cent = bs.v_cent;
+    va.cnt = bs.v_cnt;
+    va.tmp = bs.v_tmp;
+    va.tmp_bytes = tmp_bytes;
+    va.out_xyz = d_out;
+    va.out_cnt = bs.v_ocnt;
+    va.res = bs.v_res;
+    HIPCHK(launch_voxel(va, st));
+    unsigned long long res[kVoxelRes];
+    HIPCHK(hipMemcpyAsync(res, bs.v_res, sizeof res, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    VoxelOut vo;
+    vo.M = (int64_t)res[6];
+    if (vo.M <= 0) {
+        char b[128];
+        std::snprintf(b, sizeof b, "voxel filter: none of the %lld voxels holds min_points = %d points", (long long)res[7],
+                      min_points);
+        throw Fail{GICP_E_INVALID, b};
+    }
+    for (int a = 0; a < dim; ++a) {
+        vo.mn[a] = dec_ordered(res[a]);
+        vo.mx[a] = dec_ordered(res[3 + a]);
+    }
+    return vo;
+}
+
+void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
+                bool graph, BuildScratch& bs, hipStream_t st, bool staged, int cov_shard, int cov_nshards, int tile_points,
+                const std::function<void(const char*)>& tick, bool verbose, std::string& tlog);
+
+// cov_shard / cov_nshards: the covariances are computed for that shard's tiles only (a sharded source: every
+// rank needs the whole cloud's index for the neighbourhoods, but only its own tiles' covariances); the other
+// rows read NaN.
+// tile_points: points per tile at most (64; a source may take 32 or 16: GICP_SRC_TILE, DESIGN.md §5)
+// leaf > 0: the uploaded cloud is first reduced to one centroid per voxel holding >= min_points points (the
+// voxel filter, on the device), and the index is built over those centroids in key order.
+// This is the host front: the bounds and finiteness scan and the upload; build_core does the rest from the
+// device buffer bs.s_in and the bounds.
+void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_params& p, bool graph,
+                 BuildScratch& bs, hipStream_t st, bool staged = false, int cov_shard = 0, int cov_nshards = 1,
+                 int tile_points = kTile, double leaf = 0.0, int min_points = 1) {
+    if (!xyz || n <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
+    if (n > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cloud too large (> 2^31 points)"};
+    const bool verbose = std::getenv("GICP_VERBOSE") && std::getenv("GICP_VERBOSE")[0] == '1';
+    auto tprev = std::chrono::steady_clock::now();
+    std::string tlog;
+    const std::function<void(const char*)> tick = [&](const char* what) {
+        if (!verbose) return;
+        HIPCHK(hipStreamSynchronize(st));
+        const auto t = std::chrono::steady_clock::now();
+        char b[64];
+        std::snprintf(b, sizeof b, " %s %.1f", what, std::chrono::duration<double, std::milli>(t - tprev).count());
+        tlog += b;
+        tprev = t;
+    };
+    cl.n = 0;   // buffers are kept (grow-only) and reused
+    cl.cov_ready = false;
+    cl.graph_ready = false;
+    cl.dim = dim;
+    cl.bits = dim == 3 ? 10 : 16;
+    double mn[3], mx[3];
+    scan_bounds(xyz, n, dim, mn, mx);
+    tick("host-scan");
+    dreserve(bs.s_in, bs.cap_in, (size_t)n * dim);
+    // (a staged build passes its pinned copy: the H2D copy is then asynchronous)
+    if (leaf > 0.0) {
+        dreserve(bs.v_raw, bs.cap_vraw, (size_t)n * dim);
+        HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
+        const VoxelOut vo = voxel_filter(bs, bs.v_raw, n, dim, mn, mx, leaf, min_points, bs.s_in, st);
+        n = vo.M;
+        for (int a = 0; a < 3; ++a) mn[a] = vo.mn[a], mx[a] = vo.mx[a];
+        tick("voxel");
+    } else {
+        HIPCHK(hipMemcpyAsync(bs.s_in, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
+    }
+    build_core(cl, n, dim, mn, mx, p, graph, bs, st, staged, cov_shard, cov_nshards, tile_points, tick, verbose, tlog);
+}
+
+// The core of a cloud build: the n points in bs.s_in ([n][dim], device) with bounds mn / mx -> Morton sort,
+// tiles, blocks, covariances and (graph) the neighbour graph.
+void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
+                bool graph, BuildScratch& bs, hipStream_t st, bool staged, int cov_shard, int cov_nshards, int tile_points,
+                const std::function<void(const char*)>& tick, bool verbose, std::string& tlog) {
     double ext = 0.0;
     for (int a = 0; a < dim; ++a) ext = std::max(ext, mx[a] - mn[a]);
     ext = ext * (1.0 + 1e-9) + 1e-12 * (1.0 + std::fabs(mn[0]));
     for (int a = 0; a < 3; ++a) cl.lo[a] = a < dim ? mn[a] : 0.0;
     cl.scale = std::ldexp(1.0, cl.bits) / ext;
-    tick("host-scan");
 
     {
         cl.reserve_points(n);
-        dreserve(bs.s_in, bs.cap_in, (size_t)n * dim);
         dreserve(bs.s_codes, bs.cap_codes, (size_t)n);
         dreserve(bs.s_codes2, bs.cap_codes2, (size_t)n);
         dreserve(bs.s_idx, bs.cap_idx, (size_t)n);
@@ -675,8 +840,6 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
         double* d_in = bs.s_in;
         uint32_t *d_codes = bs.s_codes, *d_codes_s = bs.s_codes2;
         int32_t* d_idx = bs.s_idx;
-        // (a staged build passes its pinned copy: the H2D copy is then asynchronous)
-        HIPCHK(hipMemcpyAsync(d_in, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
         DevCloud fr = cl.view();
         HIPCHK(launch_morton(d_in, n, dim, fr, d_codes, d_idx, st));
         size_t tmp_bytes = 0;
@@ -1318,7 +1481,8 @@ int gicp_set_target(gicp_ctx* c, const double* xyz, int64_t M, int dim, const gi
     return guard_impl(c, "gicp_set_target", [&] {
         c->ptgt = resolve(dim, p);
         c->top_ready = false;
-        build_cloud(c->tgt, xyz, M, dim, c->ptgt, c->use_graph && c->use_certs, c->bs, c->stream);
+        build_cloud(c->tgt, xyz, M, dim, c->ptgt, c->use_graph && c->use_certs, c->bs, c->stream, false, 0, 1, kTile,
+                    c->voxel_leaf, c->voxel_min);
         if (c->src.n) reset_tile_state(c);
     });
 }
@@ -1330,7 +1494,8 @@ int gicp_set_source(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gi
         if (nshards < 1 || shard < 0 || shard >= nshards) throw Fail{GICP_E_INVALID, "bad shard / nshards"};
         c->psrc = resolve(dim, p);
         c->top_ready = false;
-        build_cloud(c->src, xyz, N, dim, c->psrc, false, c->bs, c->stream, false, shard, nshards, c->src_tile);
+        build_cloud(c->src, xyz, N, dim, c->psrc, false, c->bs, c->stream, false, shard, nshards, c->src_tile,
+                    c->voxel_leaf, c->voxel_min);
         set_shard(c, shard, nshards);
         HIPCHK(hipStreamSynchronize(c->stream));
     });
@@ -1696,7 +1861,8 @@ void staged_worker(gicp_ctx::Staged* gp) {
         std::string err;
         try {
             HIPCHK(hipSetDevice(gp->device));
-            build_cloud(gp->cl, gp->xyz, gp->M, gp->dim, gp->p, gp->graph, gp->bs, gp->stream, true);
+            build_cloud(gp->cl, gp->xyz, gp->M, gp->dim, gp->p, gp->graph, gp->bs, gp->stream, true, 0, 1, kTile,
+                        gp->voxel_leaf, gp->voxel_min);
         } catch (const Fail& f) {
             rc = f.code;
             err = f.msg;
@@ -1765,6 +1931,8 @@ int gicp_stage_target_ex(gicp_ctx* c, const double* xyz, int64_t M, int dim, con
             g.dim = dim;
             g.graph = c->use_graph && c->use_certs;
             g.device = c->device;
+            g.voxel_leaf = c->voxel_leaf;
+            g.voxel_min = c->voxel_min;
             g.p = prm;
             g.rc = GICP_OK;
             g.err.clear();
@@ -1979,6 +2147,60 @@ int gicp_rotated_covariances(gicp_ctx* c, int which, const double* R, double* ou
         const size_t m = (size_t)cl.n * d * d;
         dreserve(c->d_rot, c->cap_rot, m);
         HIPCHK(launch_rotate_cov(cl.cov, cl.perm, cl.n, d, R, c->d_rot, c->stream));
+        HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int gicp_set_voxel(gicp_ctx* c, double leaf, int min_points) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_set_voxel", [&] {
+        if (!std::isfinite(leaf) || leaf < 0.0) throw Fail{GICP_E_INVALID, "leaf must be finite and >= 0 (0 turns the filter off)"};
+        if (min_points < 1) throw Fail{GICP_E_INVALID, "min_points must be >= 1"};
+        c->voxel_leaf = leaf;
+        c->voxel_min = min_points;
+    });
+}
+
+int gicp_voxel_downsample(gicp_ctx* c, const double* xyz, int64_t N, int dim, double leaf, int min_points,
+                          double* out_xyz, int32_t* out_count, int64_t* M_out) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_voxel_downsample", [&] {
+        if (!xyz || N <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
+        if (N > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cloud too large (> 2^31 points)"};
+        if (!out_xyz || !M_out) throw Fail{GICP_E_INVALID, "out_xyz and M_out must not be NULL"};
+        if (!std::isfinite(leaf) || leaf <= 0.0) throw Fail{GICP_E_INVALID, "leaf must be finite and > 0"};
+        if (min_points < 1) throw Fail{GICP_E_INVALID, "min_points must be >= 1"};
+        *M_out = 0;
+        double mn[3], mx[3];
+        scan_bounds(xyz, N, dim, mn, mx);
+        BuildScratch& bs = c->bs;
+        hipStream_t st = c->stream;
+        dreserve(bs.v_raw, bs.cap_vraw, (size_t)N * dim);
+        dreserve(bs.s_in, bs.cap_in, (size_t)N * dim);
+        HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * N * dim, hipMemcpyHostToDevice, st));
+        const VoxelOut vo = voxel_filter(bs, bs.v_raw, N, dim, mn, mx, leaf, min_points, bs.s_in, st);
+        HIPCHK(hipMemcpyAsync(out_xyz, bs.s_in, sizeof(double) * vo.M * dim, hipMemcpyDeviceToHost, st));
+        if (out_count) HIPCHK(hipMemcpyAsync(out_count, bs.v_ocnt, sizeof(int32_t) * vo.M, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        *M_out = vo.M;
+    });
+}
+
+int gicp_cloud_size(gicp_ctx* c, int which, int64_t* n) {
+    if (!c || !n || (which != 0 && which != 1)) return GICP_E_INVALID;
+    *n = (which == 0 ? c->tgt : c->src).n;
+    return GICP_OK;
+}
+
+int gicp_get_points(gicp_ctx* c, int which, double* out) {
+    if (!c || !out || (which != 0 && which != 1)) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_get_points", [&] {
+        Cloud& cl = which == 0 ? c->tgt : c->src;
+        if (!cl.n) throw Fail{GICP_E_STATE, "cloud not set"};
+        const size_t m = (size_t)cl.n * cl.dim;
+        dreserve(c->d_rot, c->cap_rot, m);
+        HIPCHK(launch_points_out(cl.xyz64, cl.perm, cl.n, cl.dim, c->d_rot, c->stream));
         HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     });

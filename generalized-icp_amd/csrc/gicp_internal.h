@@ -299,6 +299,35 @@ struct CorrArgs {
 // near tie, [14] walking lanes, [15] walking waves
 constexpr int kTailWords = 16;
 
+// Voxel-grid filter (gicp_voxel.hip): the cell of a point is c_a = floor(x_a / leaf) on an
+// absolute grid; its key packs c_a - cmin_a, bits[a] bits per axis, x most significant, so ascending keys are
+// the lexicographic order of the cells.  All pointers device memory; the scratch arrays hold n entries.
+constexpr int kVoxelRes = 8;       // result words: ordered-integer min[3], max[3] of the kept centroids, M, voxels
+struct VoxelArgs {
+    const double* raw;        // [n][dim] the unfiltered cloud
+    int64_t n;
+    int32_t dim;
+    int32_t min_points;       // voxels with fewer points are dropped
+    double leaf;
+    double cmin[3];           // floor(min_a / leaf): the lowest cell per axis
+    int32_t bits[3];          // key bits per axis (0 when the axis spans one cell)
+    int32_t end_bit;          // bits the sort covers (>= 1)
+    uint64_t *keys, *keys_s;  // [n] keys, unsorted and sorted
+    int32_t *idx, *idx_s;     // [n] original indices (idx: later the scan of the keep flags)
+    int32_t* flag;            // [n] head flags (later the keep flags)
+    int32_t* vid1;            // [n] voxel id + 1 of each sorted point
+    double* cfirst;           // [ceil(n / 64)][4] per-wave carries: the sum before the wave's first head ...
+    double* clast;            // [ceil(n / 64)][4] ... and of its final segment
+    int2* cmeta;              // [ceil(n / 64)] (the wave holds a head, voxel of its final segment)
+    double* cent;             // [n][3] centroid per voxel
+    int32_t* cnt;             // [n] points per voxel
+    void* tmp;                // rocPRIM scratch (voxel_temp_bytes)
+    size_t tmp_bytes;
+    double* out_xyz;          // [M][dim] kept centroids in key order
+    int32_t* out_cnt;         // [M] their counts
+    unsigned long long* res;  // [kVoxelRes]
+};
+
 constexpr int nstat(int D) {
     return (D * (D + 1) / 2) * (D * (D + 1) / 2) + (D * (D + 1) / 2) * D + (D * (D + 1) / 2) + D * D + D + 2;
 }

@@ -22,7 +22,7 @@ from . import _lib
 from ._lib import Debug, Params, Result, Trace, check, dptr
 
 __all__ = ["gicp", "apply_transformation", "Engine", "RotatedCovariances", "expand_stats", "stats_size",
-           "default_params", "last_result"]
+           "default_params", "last_result", "voxel_downsample"]
 
 
 def stats_size(dim):
@@ -116,6 +116,7 @@ class Engine:
         self._staged = []          # (shape, params, borrowed array or None) of the staged targets, oldest first
         self._hook = None          # keeps the ctypes callback of set_allreduce alive
         self._hook_fn = None       # (fn, nranks, rank) of that hook, to restore it after a gicp() call
+        self.voxel = (0.0, 1)      # (voxel_size, min_points) of set_voxel; size 0: no filter
 
     def close(self):
         if self._ctx:
@@ -176,6 +177,8 @@ class Engine:
         check(self._lib.gicp_set_target(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p)), self._ctx,
               "gicp_set_target")
         self.n_tgt, self.dim = a.shape
+        if self.voxel[0] > 0:
+            self.n_tgt = self.cloud_size("target")
 
     def set_source(self, pts, params=None, shard=0, nshards=1):
         a = self._cloud(pts)
@@ -183,6 +186,8 @@ class Engine:
         check(self._lib.gicp_set_source(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), shard, nshards),
               self._ctx, "gicp_set_source")
         self.n_src, self.dim = a.shape
+        if self.voxel[0] > 0:
+            self.n_src = self.cloud_size("source")
         self.generation += 1
 
     def target_to_source(self, shard=0, nshards=1):
@@ -204,7 +209,7 @@ class Engine:
         p = params or default_params(a.shape[1])
         check(self._lib.gicp_stage_target_ex(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p),
                                              _lib.GICP_STAGE_BORROW if borrow else 0), self._ctx, "gicp_stage_target")
-        self._staged.append((a.shape, p, a if borrow else None))
+        self._staged.append((a.shape, p, a if borrow else None, self.voxel[0] > 0))
 
     def commit_target(self, shard=0, nshards=1):
         """Wait for the oldest staged target; the current target becomes the source, the staged one the target."""
@@ -215,11 +220,54 @@ class Engine:
             self.n_src = self.n_tgt
             self.generation += 1
         self.n_tgt, self.dim = staged[0]
+        if staged[3]:   # staged with a voxel filter set: the target holds the filtered cloud
+            self.n_tgt = self.cloud_size("target")
 
     def cancel_stage(self):
         """Wait for and drop every staged target."""
         self._lib.gicp_cancel_stage(self._ctx)
         self._staged = []
+
+    def set_voxel(self, voxel_size, min_points=1):
+        """Voxel-grid filter of every cloud set or staged from now on (gicp_set_voxel): each is reduced on
+        the device to one centroid per occupied cell of the absolute grid floor(x / voxel_size), cells
+        with fewer than min_points points dropped, before its index is built.  voxel_size None or 0 turns
+        the filter off.  With a filter, every per-point output of this engine (covariances,
+        neighbor_counts, graph, iterate's index / weight / distance, the top weights) refers to the rows of
+        the FILTERED clouds, which points() returns: ascending lexicographic order of the cells."""
+        size = 0.0 if voxel_size is None else float(voxel_size)
+        check(self._lib.gicp_set_voxel(self._ctx, size, int(min_points)), self._ctx, "gicp_set_voxel")
+        self.voxel = (size, int(min_points))
+
+    def voxel_downsample(self, points, voxel_size, min_points=1, return_counts=False):
+        """gicp.voxel_downsample on this engine's GPU (gicp_voxel_downsample); the engine's clouds and its
+        set_voxel setting are untouched."""
+        a = self._cloud(points)
+        out = np.empty_like(a)
+        cnt = np.empty(a.shape[0], dtype=np.int32)
+        m = C.c_int64()
+        check(self._lib.gicp_voxel_downsample(self._ctx, dptr(a), a.shape[0], a.shape[1], float(voxel_size),
+                                              int(min_points), dptr(out), cnt.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              C.byref(m)), self._ctx, "gicp_voxel_downsample")
+        out = out[:m.value].copy()
+        return (out, cnt[:m.value].copy()) if return_counts else out
+
+    def cloud_size(self, which="target"):
+        """Points the indexed cloud holds (gicp_cloud_size): the input's length, or with a voxel filter
+        the number of voxels kept."""
+        n = C.c_int64()
+        check(self._lib.gicp_cloud_size(self._ctx, 0 if which == "target" else 1, C.byref(n)), self._ctx,
+              "gicp_cloud_size")
+        return int(n.value)
+
+    def points(self, which="target"):
+        """The indexed cloud's points in its original order (gicp_get_points): the input rows, or with a
+        voxel filter the centroids every per-point output refers to."""
+        n = self.cloud_size(which)
+        out = np.empty((n, self.dim))
+        check(self._lib.gicp_get_points(self._ctx, 0 if which == "target" else 1, dptr(out)), self._ctx,
+              "gicp_get_points")
+        return out
 
     def covariances(self, which="target"):
         w = 0 if which == "target" else 1
@@ -504,6 +552,17 @@ def _engine(device):
     return eng
 
 
+def voxel_downsample(points, voxel_size, min_points=1, return_counts=False, device=0):
+    """Voxel-grid downsampling on the GPU (gicp_voxel_downsample): one centroid per occupied cell of the
+    absolute grid floor(x / voxel_size), cells with fewer than min_points points dropped, in ascending
+    lexicographic order of the cells (the order of np.unique(cells, axis=0)).  N x 2 or N x 3 in, M x dim
+    out; with return_counts also the int32 number of points behind each centroid.  Deterministic: the same
+    input gives the same bits on every call and every GPU.  Raises ValueError for a voxel_size that is
+    not finite and positive, non-finite points, a cloud spanning more than 2^21 (3-D) / 2^31 (2-D) cells
+    along an axis, and when no cell reaches min_points."""
+    return _engine(int(device)).voxel_downsample(points, voxel_size, min_points, return_counts)
+
+
 def _devices(device, devices):
     """The GPUs a gicp() call runs on: [device], or the distinct entries of `devices`."""
     if devices is None:
@@ -589,7 +648,8 @@ def pcl_stop(T_old, T_new, mse, prev_mse, transformation_epsilon=0.0, rotation_e
 def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_distance_correspondence=150,
          max_distance_nearest_neighbors=50, *, full_output=True, mode=None, inner=None, k_neighbors=None, device=0,
          devices=None, verbose=True, T0=None, method="plane_to_plane", transformation_epsilon=0.0,
-         rotation_epsilon=0.0, euclidean_fitness_epsilon=0.0, mse_relative_epsilon=0.0):
+         rotation_epsilon=0.0, euclidean_fitness_epsilon=0.0, mse_relative_epsilon=0.0, voxel_size=None,
+         voxel_min_points=1):
     """Drop-in for gicp.py:78 — returns the same 7-tuple (gicp.py:174):
 
     (T, all_transformations, initial_source_cov_matrices, target_cov_matrices,
@@ -624,6 +684,11 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
     transformation_epsilon / rotation_epsilon / euclidean_fitness_epsilon /
       mse_relative_epsilon: optional PCL-style stopping criteria (see pcl_stop), tested
       after the update; 0 disables each.  tolerance=0 disables the reference's rule.
+    voxel_size / voxel_min_points: None (default) registers the clouds as given.  Otherwise both are
+      first reduced on the device to one centroid per voxel_size cell holding at least voxel_min_points
+      points (voxel_downsample), and every per-point member of the 7-tuple -- the covariance arrays, the
+      highest-weight points, all_source_cov_matrices -- refers to the FILTERED clouds, whose lengths
+      differ from the inputs'.
     """
     src = Engine._cloud(source_points)
     tgt = Engine._cloud(target_points)
@@ -656,8 +721,22 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
         e.set_target(tgt, p)
         e.set_source(src, p, shard=r, nshards=G)
 
-    _run_ranks(engines, build)
-    eng = engines[0]
+    if voxel_size is None:
+        _run_ranks(engines, build)
+        eng = engines[0]
+    else:   # the engines are shared between calls: the setting lasts for this call's builds only
+        prev_voxel = [e.voxel for e in engines]
+        try:
+            for e in engines:
+                e.set_voxel(voxel_size, voxel_min_points)
+            _run_ranks(engines, build)
+            eng = engines[0]
+            # the host side of the loops (highest-weight points, the faithful mode's moved source) works on
+            # the clouds the engine registers
+            src, tgt = eng.points("source"), eng.points("target")
+        finally:
+            for e, v in zip(engines, prev_voxel):
+                e.set_voxel(*v)
     target_cov = eng.covariances("target")
     init_src_cov = eng.covariances("source")
     for e in engines[1:]:   # each device computed its own shard's source covariances (NaN elsewhere)

@@ -144,6 +144,11 @@ SIGNATURES = {
     "gicp_peer_close": (C.c_int, [_VP]),
     "gicp_build_info": (C.c_char_p, []),
     "gicp_rotated_covariances": (C.c_int, [_VP, C.c_int, _DP, _DP]),
+    "gicp_voxel_downsample": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.c_double, C.c_int, _DP, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int64)]),
+    "gicp_set_voxel": (C.c_int, [_VP, C.c_double, C.c_int]),
+    "gicp_cloud_size": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64)]),
+    "gicp_get_points": (C.c_int, [_VP, C.c_int, _DP]),
 }
 
 # gicp_allreduce_fn: int (*)(double* buf, int n, void* user)
@@ -152,7 +157,8 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, _DP, C.c_int, C.c_void_p)
 _lib = None
 
 # the sources gicp_build_info()'s hash covers, in the Makefile's HASH_SRCS order
-HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_internal.h",
+HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_voxel.hip",
+             "csrc/gicp_internal.h",
              "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "../include/gicp_hip.h")
 
 

@@ -25,7 +25,7 @@ from . import Engine, default_params
 
 class Odometry:
     def __init__(self, dim=3, params=None, device=0, composition="se3", init="constant_velocity", borrow=False,
-                 **kw):
+                 voxel_size=None, voxel_min_points=1, **kw):
         if composition not in ("se3", "reference"):
             raise ValueError("composition must be 'se3' or 'reference'")
         if init not in ("identity", "constant_velocity"):
@@ -33,6 +33,11 @@ class Odometry:
         self.dim = dim
         self.params = params if params is not None else default_params(dim, **kw)
         self.eng = Engine(device)
+        # voxel_size: every scan is reduced on the device to one centroid per voxel_size cell holding at least
+        # voxel_min_points points before it is indexed (Engine.set_voxel) -- on the staged, borrowed and
+        # synchronous paths alike; a borrowed scan is still read in place
+        if voxel_size is not None:
+            self.eng.set_voxel(voxel_size, voxel_min_points)
         self.composition = composition
         self.init = init
         # borrow=True: staged scans are read by the library in place (GICP_STAGE_BORROW, no copy on this

@@ -168,7 +168,7 @@ int gicp_peer_close(gicp_ctx* ctx);   /* back to no exchange (RCCL / hook as set
 
 /* Build provenance of this library: "src=<first 16 hex of sha256 over the sources>;git=<rev>;built=<date
  * time>;arch=gfx950".  The source hash covers csrc/{gicp_kernels.hip, gicp_capi.cpp, gicp_solver.cpp,
- * gicp_internal.h, gicp_solver.h, gicp_solve_dev.h} and include/gicp_hip.h, concatenated in that order, so
+ * gicp_cg.cpp, gicp_voxel.hip, gicp_internal.h, gicp_solver.h, gicp_solve_dev.h} and include/gicp_hip.h, concatenated in that order, so
  * a caller can prove the loaded library was compiled from the sources beside it. */
 const char* gicp_build_info(void);
 
@@ -313,6 +313,35 @@ int gicp_set_allreduce_ranks(gicp_ctx* ctx, gicp_allreduce_fn fn, void* user, in
  * point, computed on the device (gicp.py:120-121 all_source_cov_matrices, rotated instead of
  * recomputed), ORIGINAL order, [n, dim, dim].  which: 0 = target, 1 = source. */
 int gicp_rotated_covariances(gicp_ctx* ctx, int which, const double* R, double* out);
+
+/* ---- voxel-grid downsampling -------------------------------------------------------
+ * One centroid per occupied cell of an ABSOLUTE grid of edge `leaf`: the cell of a point is
+ * floor(x_a / leaf) per axis (fp64, correctly rounded division: NumPy's np.floor(x / leaf) bit for bit),
+ * so a voxel is the same region of space in every frame of a stream.  A centroid is the fp64 sum of the
+ * cell's points divided by their number; the summation order is a fixed function of the input (no
+ * floating-point atomics), so the output is bit-identical from call to call and context to context.
+ * Voxels with fewer than min_points points are dropped.  The survivors come in ascending lexicographic
+ * order of their cells (c_x, c_y[, c_z]) -- the order of np.unique(cells, axis=0).  The cloud may span at
+ * most 2^21 cells per axis in 3-D and 2^31 in 2-D.
+ *
+ * One-shot, host in, host out: out_xyz [N][dim] and out_count [N] (may be NULL) are caller-allocated for
+ * the worst case; *M_out receives the number of voxels kept (their rows come first).  GICP_E_INVALID for
+ * a leaf that is not finite or <= 0, min_points < 1, non-finite input, a cell range too wide, and when no
+ * voxel reaches min_points. */
+int gicp_voxel_downsample(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, double leaf, int min_points,
+                          double* out_xyz, int32_t* out_count, int64_t* M_out);
+/* Context setting: leaf > 0 filters every later gicp_set_target / gicp_set_source / gicp_stage_target[_ex]
+ * cloud on the device, after its upload and before its index is built (only the centroids' bounds and their
+ * number return to the host); leaf = 0, the default, is off.  A staged build uses the setting in force when
+ * it was staged, on its own stream; GICP_STAGE_BORROW still reads the caller's raw frame in place.  With a
+ * sharded source every rank filters the whole cloud (the filter is deterministic: the ranks agree).
+ * With a filter set, "original order" and "original index" of a cloud, everywhere in this header
+ * (gicp_debug.index, gicp_top_weights, gicp_get_covariances, gicp_get_graph, ...), mean the rows of the
+ * FILTERED cloud in the order above; gicp_cloud_size and gicp_get_points return their number and the rows.
+ * GICP_E_INVALID for leaf < 0 or not finite, or min_points < 1. */
+int gicp_set_voxel(gicp_ctx* ctx, double leaf, int min_points);
+int gicp_cloud_size(gicp_ctx* ctx, int which, int64_t* n);      /* points the indexed cloud holds (0: not set) */
+int gicp_get_points(gicp_ctx* ctx, int which, double* out);     /* [n][dim], the cloud's original order */
 
 #ifdef __cplusplus
 }

@@ -495,15 +495,18 @@ struct WaveStage {
     double x64[kTile], y64[kTile], z64[kTile];    // fp64 coordinates (covariance sums, fallback)
     int32_t perm[kTile];                          // original indices (fallback tie-break)
 };
-// statistics transpose image of 16 points: u[term][point] and v[term][point], rows padded to 17 doubles
-// (a term's 16 points are written by 16 lanes to consecutive words; the MFMA operand reads of a row
-// group spread over the banks)
+// statistics transpose image of 32 points (half a wave): u[term][point] and v[term][point], rows padded
+// to 33 doubles.  A term's 32 points are written by 32 lanes to consecutive words.  An MFMA operand read
+// takes row l & 15 at column c + (l >> 4); the compiler pairs the reads of two MFMAs into ds_read2_b64
+// (banks of 4 B modulo 32, conflicts within 16 consecutive lanes, which share l >> 4): rows r = 0..15 at
+// doubles 33 r + const fall on the bank pairs 2 r + const, all distinct.  An even stride collides: 34 put
+// rows r and r + 8 on one bank (SQ_LDS_BANK_CONFLICT 124 cycles per wave against 6 at 33 and at the former
+// 17, profiles/epilogue/README.md); lone ds_read_b64 (modulo 64, 32-lane halves) would want 34 instead.
 // Only the rows of terms in use are stored (12 u and 10 v terms in 3-D): the MFMA lanes of the unused
 // rows read a duplicate of the last row, whose products land in output rows / columns nobody reads.
-// 22 x 17 doubles (2992 B) instead of 2 x 16 x 17: with the walk's staging (2560 B) in the same union
-// and the wave's statistics written into it after the GEMM, a workgroup takes 12 KB of LDS, 13 per CU
-// instead of 8 -- a CU whose resident workgroups each wait on one long-walking wave can start others.
-constexpr int kStatRow = 17;
+// 22 x 33 doubles (5808 B) per wave: two transposes per wave instead of four, at 22.7 KB of LDS per
+// workgroup -- the six workgroups that 80 VGPRs allow on a CU take 136 of its 160 KiB.
+constexpr int kStatRow = 33;
 constexpr int kStatU = 12, kStatV = 10;
 struct WaveStat {
     double u[kStatU * kStatRow];
@@ -1246,6 +1249,60 @@ struct StatIdx {
     }
 };
 
+// Where entry (p, q) of the statistics GEMM's 16x16 product u v^T goes in the statistics vector (DESIGN.md
+// §4), or kNoSlot: most of the product is not a statistic.  Each statistic has exactly one (p, q).
+constexpr int kNoSlot = 0xFF;
+template <int D>
+constexpr int stat_slot(int p, int q) {
+    constexpr int NS = D * (D + 1) / 2;
+    constexpr int oB = NS * NS, oC = oB + NS * D, oR = oC + NS, oT = oR + D * D, o0 = oT + D;
+    if (p < NS) {
+        if (q < NS) return p * NS + q;                       // A[ab][ij]
+        if (q < NS + D) return oB + p * D + (q - NS);        // B[ab][i]
+        if (q == NS + D) return oC + p;                      // C[ab]
+    } else if (p < NS + D) {
+        if (q >= NS && q < NS + D) return oR + (p - NS) * D + (q - NS);   // gR[a][i]
+        if (q == NS + D) return oT + (p - NS);                            // gt[a]
+    } else if (q == NS + D) {
+        if (p <= NS + D + 1) return o0 + (p - NS - D);       // c0, count
+        if (p == NS + D + 2) return nstat(D) + 3;            // sum |r|^2 (extended slot)
+    }
+    return kNoSlot;
+}
+// Lane l of v_mfma_f64_16x16x4_f64 holds product entries (p = (l >> 4) + 4 j, q = l & 15), j = 0..3: their
+// slots, one byte each (byte j), as one dword per lane
+template <int D>
+struct StatSlots {
+    uint32_t lane[64];
+    constexpr StatSlots() : lane{} {
+        for (int l = 0; l < 64; ++l) {
+            uint32_t w = 0;
+            for (int j = 0; j < 4; ++j) w |= (uint32_t)stat_slot<D>((l >> 4) + 4 * j, l & 15) << (8 * j);
+            lane[l] = w;
+        }
+    }
+};
+static_assert(nstat_ext(3) <= kNoSlot && nstat_ext(2) <= kNoSlot, "a statistic's slot fits a byte");
+// every statistic, and the extended sum |r|^2, has one owner among the 256 entries; no other slot is written
+template <int D>
+constexpr bool stat_slots_one_owner() {
+    int owners[kNoSlot] = {};
+    for (int p = 0; p < 16; ++p)
+        for (int q = 0; q < 16; ++q)
+            if (stat_slot<D>(p, q) != kNoSlot) ++owners[stat_slot<D>(p, q)];
+    for (int k = 0; k < kNoSlot; ++k)
+        if (owners[k] != ((k < nstat(D) || k == nstat(D) + 3) ? 1 : 0)) return false;
+    return true;
+}
+static_assert(stat_slots_one_owner<2>() && stat_slots_one_owner<3>(), "one owner lane per statistic");
+__device__ const StatSlots<2> kStatSlots2{};
+__device__ const StatSlots<3> kStatSlots3{};
+template <int D>
+__device__ __forceinline__ uint32_t stat_slots(int l) {
+    if constexpr (D == 2) return kStatSlots2.lane[l];
+    else return kStatSlots3.lane[l];
+}
+
 // statistic k of one point: A[ab][ij], B[ab][i], C[ab], gR[a][i], gt[a], c0, count
 template <int D>
 __device__ __forceinline__ double stat_value(int k, const double (&W)[D][D], const double (&s)[D],
@@ -1496,7 +1553,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
 
         // seed: last pass's best target tile for this source tile, else the Morton neighbour
         int seed = hint0;
-        if (seed < 0 || seed >= tg.ntiles) {
+        if (__builtin_expect(seed < 0 || seed >= tg.ntiles, 0)) {   // a tile's first pass only
             const uint32_t code = morton_code(q.ow, D, tg.lo, tg.scale, tg.bits);
             int lo = 0, hi = tg.ntiles - 1;
             if (tg.seed_tab) {   // the bucket's range: both ends in one round trip
@@ -1781,7 +1838,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
             // near ties: every candidate of the tie node's row (and the node) exactly in fp64, the nearest
             // by the KD-tree's tie rule (smaller original index); the lane's certificate gap is the exact
             // runner-up among them, or the row's reach when that is nearer
-            if (wave_any(tie)) {
+            if (__builtin_expect(wave_any(tie), 0)) {
                 if (tie) {
                     double p64[D];
                     {
@@ -1885,7 +1942,10 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
             if (!q.valid || cert) return -1.f;
             return fminf(cap, fminf(key_d2(sec), bound_of(key_d2(best))));
         };
-        float lb = lane_bound();   // refreshed after every merge
+        // refreshed after every merge; -1 on every lane of a wave that skips the walk (each is certified or
+        // has no query), which is what lane_bound() would give: its arithmetic is left out there
+        float lb = -1.f;
+        if (!skip_walk) lb = lane_bound();
 #ifdef GICP_TIMELINE
         S.wb0 = __builtin_amdgcn_sqrtf(fmaxf(wave_maxf(lb), 0.f));
 #endif
@@ -1895,7 +1955,8 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
             const float r = __builtin_amdgcn_sqrtf(w) * 1.0001f + 2.f * A.gap_slack;
             return r * r;
         };
-        float lbx = inflate(lb);
+        float lbx = -1.f;
+        if (!skip_walk) lbx = inflate(lb);
         // lane k: list entry k once the list walk has visited it; a full walk that continues a list walk
         // whose certificate failed skips those tiles (their rows are already in every lane's best and
         // runner-up; -1 elsewhere, so no other walk skips anything)
@@ -2271,7 +2332,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
         }
 
         // ---- fp64 re-resolution of the lanes the screen could not decide ----
-        if (!skip_walk && __any(amb)) {
+        if (__builtin_expect(!skip_walk && __any(amb), 0)) {   // rare: laid out behind the epilogue
             double bd2 = 1e300;   // exact best d^2 among the rows scanned
             float sd2 = 3e38f;    // runner-up d^2, rounded down (a lower bound is all a certificate needs)
             int bj = -1;   // its sorted index; the original index (tie-break) is read only on exact ties
@@ -2286,10 +2347,13 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
                 stage_f64(tg, ti, L);
                 if (l < ti.count) L.t.perm[l] = tg.perm[ti.start + l];
                 wave_sync();
+                // rolled: a rare path (waves with more than sparse_amb ambiguous lanes) whose unrolled copies,
+                // one per inlined call, were 17 KB of the 3-D kernel's 93 KB of code
+#pragma unroll 1
                 for (int g = 0; g < kSub; ++g) {
                     if (!((sub >> g) & 1u)) continue;
                     const int je = min(kSubRows * g + kSubRows, ti.count);
-#pragma unroll 4
+#pragma unroll 1
                     for (int jj = kSubRows * g; jj < je; ++jj) {
                         const double qq[3] = {L.t.x64[jj], L.t.y64[jj], L.t.z64[jj]};
                         const double d2 = dist2_exact<D>(qq, q.p64);
@@ -2546,7 +2610,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
     S.mark(5);
     // ---- wave reduction of the statistics: a 16x16x64 fp64 GEMM on MFMA ---------------------
     // stats[p][q] = sum over lanes of u_p v_q with u = (W sym, W r, r^T W r, 1, |r|^2), v = (s s sym, s,
-    // 1).  Points are transposed through LDS 16 at a time as u[term][point] /
+    // 1).  Points are transposed through LDS 32 at a time as u[term][point] /
     // v[term][point]: lane = point writes its terms to one column (every address a constant offset of
     // one base, no per-write address arithmetic), lane l reads A[p = l&15][k = l>>4] /
     // B[k][q = l&15] of v_mfma_f64_16x16x4_f64 from row l&15 at a constant offset per MFMA.
@@ -2572,19 +2636,24 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
         typedef double d4v __attribute__((ext_vector_type(4)));
         d4v acc = {0.0, 0.0, 0.0, 0.0};
         WaveStat& X = s_lds[w].st;
-        // points that contribute nothing (rejected, or the tile's padding lanes) have u = 0: a group
-        // of 16 or an MFMA's 4 points with none accepted adds exact zeros and is skipped (uniform test)
+        // points that contribute nothing (rejected, or the tile's padding lanes) have u = 0: a half
+        // of the wave with none accepted adds exact zeros and is skipped (uniform test).  Inside a
+        // half every MFMA runs: four points of zeros leave the accumulator, which starts at +0.0, as
+        // it is
         static_assert(NU <= kStatU && NV <= kStatV, "statistics terms fit the transpose image");
         const uint64_t onm = __ballot(on);
+        const uint32_t slots = stat_slots<D>(l);   // requested here: in by the time the GEMM is done
         wave_sync();
-        double* const wu = &X.u[l & 15];
-        double* const wv = &X.v[l & 15];
+        double* const wu = &X.u[l & 31];
+        double* const wv = &X.v[l & 31];
         const double* const ru = &X.u[min(l & 15, NU - 1) * kStatRow + (l >> 4)];
         const double* const rv = &X.v[min(l & 15, NV - 1) * kStatRow + (l >> 4)];
+        // two phases of 32 points; the 8 MFMAs of a phase take the points in the order 4 cc + (l >> 4),
+        // cc = 0..7, so the accumulator sums the wave's 64 points in ascending groups of four
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            if (((onm >> (16 * g)) & 0xFFFFull) == 0) continue;
-            if ((l >> 4) == g) {
+        for (int h = 0; h < 2; ++h) {
+            if ((uint32_t)(onm >> (32 * h)) == 0u) continue;
+            if ((l >> 5) == h) {
 #pragma unroll
                 for (int k = 0; k < NU; ++k) wu[k * kStatRow] = uel(k);
 #pragma unroll
@@ -2592,10 +2661,8 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
             }
             wave_sync();
 #pragma unroll
-            for (int cc = 0; cc < 4; ++cc) {
-                if (((onm >> (16 * g + 4 * cc)) & 0xFull) == 0) continue;
+            for (int cc = 0; cc < 8; ++cc)
                 acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ru[4 * cc], rv[4 * cc], acc, 0, 0, 0);
-            }
             wave_sync();
         }
         // lane l holds stats[p = (l>>4) + 4j][q = l&15], j = 0..3; the GEMM's operands are read, so the
@@ -2604,21 +2671,8 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
         for (int k = l; k < NSX; k += 64) wst[k] = 0.0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const int p = (l >> 4) + 4 * j, qq = l & 15;
-            int idx = -1;
-            if (p < NS) {
-                if (qq < NS) idx = p * NS + qq;
-                else if (qq < NS + D) idx = NS * NS + p * D + (qq - NS);
-                else if (qq == NS + D) idx = NS * NS + NS * D + p;
-            } else if (p < NS + D) {
-                if (qq >= NS && qq < NS + D) idx = NS * NS + NS * D + NS + (p - NS) * D + (qq - NS);
-                else if (qq == NS + D) idx = NS * NS + NS * D + NS + D * D + (p - NS);
-            } else if (qq == NS + D && p <= NS + D + 1) {
-                idx = NS * NS + NS * D + NS + D * D + D + (p - NS - D);   // c0, count
-            } else if (qq == NS + D && p == NS + D + 2) {
-                idx = NSS + 3;                                            // sum |r|^2
-            }
-            if (idx >= 0) wst[idx] = acc[j];   // each (p,q) has one owner lane: no race
+            const int idx = (int)((slots >> (8 * j)) & 0xFFu);   // stat_slot<D>((l >> 4) + 4 j, l & 15)
+            if (idx != kNoSlot) wst[idx] = acc[j];   // each statistic has one owner lane: no race
         }
         namb_total += (int)__popcll(__ballot(amb));
     }

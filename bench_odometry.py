@@ -2,6 +2,7 @@
 (64 x 1563 rays ~ 100k points per frame) through the C2 room, one MI355X.
 
     python bench_odometry.py [--frames 1000] [--max-iterations 30] [--fixed]
+    python bench_odometry.py --map-voxel 0.4 --map-range 30     # the same stream, scan-to-map
 
 Prints one JSON line: GICP iterations/sec over the registration loops, frames/sec end to end
 (upload + index + covariances + registration per frame), setup per frame, and the trajectory
@@ -35,7 +36,14 @@ def main():
                          "memory, lends them (GICP_STAGE_BORROW: no copy on the calling thread)")
     ap.add_argument("--voxel-size", type=float, default=None,
                     help="voxel-filter every scan on the device before it is indexed (metres; default: off)")
+    ap.add_argument("--map-voxel", type=float, default=None,
+                    help="scan-to-map mode: every scan is registered against a local voxel map of this leaf (metres) "
+                         "and merged into it (needs --map-range; default: scan-to-scan)")
+    ap.add_argument("--map-range", type=float, default=None, help="reach of the local map from the sensor (metres)")
+    ap.add_argument("--map-min-points", type=int, default=1, help="voxels with fewer points are not registered against")
     a = ap.parse_args()
+    if (a.map_voxel is None) != (a.map_range is None):
+        ap.error("--map-voxel and --map-range go together")
     from gicp import synthetic as S
     from gicp.odometry import Odometry
     xp, dev = None, None
@@ -56,7 +64,8 @@ def main():
         # no per-launch HIP event pairs (a diagnostic the line does not report: each pair is queue work between
         # two launches); --kernel-times keeps the library default (every 8th launch timed)
         p.timing_stride = -1
-    odo = Odometry(3, params=p, borrow=not a.copy, voxel_size=a.voxel_size)
+    odo = Odometry(3, params=p, borrow=not a.copy, voxel_size=a.voxel_size, map_voxel_size=a.map_voxel,
+                   map_range=a.map_range, map_min_points=a.map_min_points)
     # warm-up on the first two frames (library init, allocation), then restart the stream
     odo.step(frames[0][0])
     odo.step(frames[1][0], frames[2][0])
@@ -112,7 +121,17 @@ def main():
                                            for k in range(1, len(frames))))},
     }
     if a.voxel_size is not None:
-        line["voxel"] = {"voxel_size": a.voxel_size, "points_last_frame": odo.eng.cloud_size("target")}
+        line["voxel"] = {"voxel_size": a.voxel_size, "points_last_frame": odo.eng.cloud_size("source" if a.map_voxel else "target")}
+    if a.map_voxel is not None:
+        tm, nf = odo.timing, a.frames
+        line["metric"] = "GICP iterations/sec, scan-to-map odometry stream (C5)"
+        line["pipeline"] = "scan-to-map: source build, align against the map, insert, synchronous target rebuild"
+        line["map"] = {"voxel_size": a.map_voxel, "range": a.map_range, "min_points": a.map_min_points,
+                       "voxels_last_frame": odo.eng.map_size(), "target_points_last_frame": odo.eng.cloud_size("target"),
+                       "source_build_ms_per_frame": tm["setup_s"] * 1e3 / nf,
+                       "align_ms_per_frame": tm["align_s"] * 1e3 / max(1, nf - 1),
+                       "insert_ms_per_frame": tm["map_insert_s"] * 1e3 / nf,
+                       "target_rebuild_ms_per_frame": tm["map_target_s"] * 1e3 / nf}
     print(json.dumps(line))
 
 

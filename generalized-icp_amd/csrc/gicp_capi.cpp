@@ -46,6 +46,9 @@ hipError_t launch_top_weights(const double*, const int64_t*, const int32_t*, int
 hipError_t voxel_temp_bytes(int64_t, int, size_t*, hipStream_t);
 hipError_t launch_voxel(const VoxelArgs&, hipStream_t);
 hipError_t launch_points_out(const double*, const int32_t*, int64_t, int, double*, hipStream_t);
+hipError_t launch_map_insert(const VoxelArgs&, const MapArgs&, hipStream_t);
+hipError_t launch_map_centroids(const double*, int64_t, int, int, int32_t*, int32_t*, void*, size_t, double*,
+                                unsigned long long*, hipStream_t);
 int corr_grid(int q_tiles, int shard, int nshards);
 int solve_pose(int d, const double* st, const double* Tk, double* Tout, double* loss_out);
 }  // namespace gicp
@@ -321,6 +324,36 @@ struct BuildScratch {
     }
 };
 
+// The local voxel map (gicp_map_*): rows (cell, sums, count) in key order, double-buffered --
+// an insert reads buffer `cur` and writes the other -- and grow-only like the build scratch.
+struct VoxelMap {
+    bool set = false;                 // gicp_map_reset was called
+    int dim = 0;
+    double leaf = 0.0;
+    int64_t R = 0;                    // half-width of the window in cells
+    int bits = 0;                     // key bits per axis: ceil(log2(2 R + 1))
+    int64_t rows = 0;
+    int cur = 0;
+    int32_t* cells[2] = {nullptr, nullptr};   // [rows][3]
+    double* sums[2] = {nullptr, nullptr};     // [rows][4]
+    size_t cap_cells[2] = {0, 0}, cap_sums[2] = {0, 0};
+    double* pts = nullptr;            // [n][dim] the scan being inserted, original order
+    double* vals = nullptr;           // [rows + n][4] staged values of an insert
+    size_t cap_pts = 0, cap_vals = 0;
+    void release() {
+        for (int b = 0; b < 2; ++b) {
+            dfree(cells[b]);
+            dfree(sums[b]);
+            cap_cells[b] = cap_sums[b] = 0;
+        }
+        dfree(pts);
+        dfree(vals);
+        cap_pts = cap_vals = 0;
+        rows = 0;
+        set = false;
+    }
+};
+
 }  // namespace
 
 struct gicp_ctx {
@@ -380,6 +413,7 @@ struct gicp_ctx {
     // voxel filter of every later cloud build (gicp_set_voxel): leaf 0 = off
     double voxel_leaf = 0.0;
     int voxel_min = 1;
+    VoxelMap map;                     // local voxel map (gicp_map_reset)
     // staged targets (gicp_stage_target / gicp_commit_target): a ring of GICP_MAX_STAGED slots, each
     // built into its own cloud on its own stream by a host thread while the current target is
     // registered; commits take them in staging order
@@ -681,6 +715,46 @@ struct VoxelOut {
     double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};   // bounds of their centroids
 };
 
+// The filter's scratch for va.n rows sorted on va.end_bit key bits, reserved (grow-only) and entered into va;
+// centroids: also the per-voxel centroids and counts (the map's inserts store sums instead).
+void voxel_scratch(BuildScratch& bs, VoxelArgs& va, bool centroids, hipStream_t st) {
+    const int64_t n = va.n;
+    const size_t nw = (size_t)((n + kWave - 1) / kWave);
+    dreserve(bs.v_keys, bs.cap_vkeys, (size_t)n);
+    dreserve(bs.v_keys2, bs.cap_vkeys2, (size_t)n);
+    dreserve(bs.v_idx, bs.cap_vidx, (size_t)n);
+    dreserve(bs.v_idx2, bs.cap_vidx2, (size_t)n);
+    dreserve(bs.v_flag, bs.cap_vflag, (size_t)n);
+    dreserve(bs.v_vid, bs.cap_vvid, (size_t)n);
+    if (centroids) {
+        dreserve(bs.v_cnt, bs.cap_vcnt, (size_t)n);
+        dreserve(bs.v_ocnt, bs.cap_vocnt, (size_t)n);
+        dreserve(bs.v_cent, bs.cap_vcent, (size_t)n * 3);
+    }
+    dreserve(bs.v_cfirst, bs.cap_vcf, nw * 4);
+    dreserve(bs.v_clast, bs.cap_vcl, nw * 4);
+    dreserve(bs.v_cmeta, bs.cap_vcm, nw);
+    if (!bs.v_res) dalloc(bs.v_res, (size_t)kVoxelRes);
+    size_t tmp_bytes = 0;
+    HIPCHK(voxel_temp_bytes(n, va.end_bit, &tmp_bytes, st));
+    dreserve(bs.v_tmp, bs.cap_vtmp, tmp_bytes + 16);
+    va.keys = bs.v_keys;
+    va.keys_s = bs.v_keys2;
+    va.idx = bs.v_idx;
+    va.idx_s = bs.v_idx2;
+    va.flag = bs.v_flag;
+    va.vid1 = bs.v_vid;
+    va.cfirst = bs.v_cfirst;
+    va.clast = bs.v_clast;
+    va.cmeta = bs.v_cmeta;
+    va.cent = centroids ? bs.v_cent : nullptr;
+    va.cnt = centroids ? bs.v_cnt : nullptr;
+    va.tmp = bs.v_tmp;
+    va.tmp_bytes = tmp_bytes;
+    va.out_cnt = centroids ? bs.v_ocnt : nullptr;
+    va.res = bs.v_res;
+}
+
 // The voxel filter (gicp_voxel.hip) of the device cloud d_raw [n][dim] with host bounds mn / mx:
 // centroids of the voxels holding >= min_points points into d_out [M][dim] in key order, their counts into
 // bs.v_ocnt.  One stream sync; the result words (centroid bounds, M) are all that returns to the host.
@@ -713,39 +787,8 @@ VoxelOut voxel_filter(BuildScratch& bs, const double* d_raw, int64_t n, int dim,
         total += bits;
     }
     va.end_bit = std::max(1, total);
-    const size_t nw = (size_t)((n + kWave - 1) / kWave);
-    dreserve(bs.v_keys, bs.cap_vkeys, (size_t)n);
-    dreserve(bs.v_keys2, bs.cap_vkeys2, (size_t)n);
-    dreserve(bs.v_idx, bs.cap_vidx, (size_t)n);
-    dreserve(bs.v_idx2, bs.cap_vidx2, (size_t)n);
-    dreserve(bs.v_flag, bs.cap_vflag, (size_t)n);
-    dreserve(bs.v_vid, bs.cap_vvid, (size_t)n);
-    dreserve(bs.v_cnt, bs.cap_vcnt, (size_t)n);
-    dreserve(bs.v_ocnt, bs.cap_vocnt, (size_t)n);
-    dreserve(bs.v_cent, bs.cap_vcent, (size_t)n * 3);
-    dreserve(bs.v_cfirst, bs.cap_vcf, nw * 4);
-    dreserve(bs.v_clast, bs.cap_vcl, nw * 4);
-    dreserve(bs.v_cmeta, bs.cap_vcm, nw);
-    if (!bs.v_res) dalloc(bs.v_res, (size_t)kVoxelRes);
-    size_t tmp_bytes = 0;
-    HIPCHK(voxel_temp_bytes(n, va.end_bit, &tmp_bytes, st));
-    dreserve(bs.v_tmp, bs.cap_vtmp, tmp_bytes + 16);
-    va.keys = bs.v_keys;
-    va.keys_s = bs.v_keys2;
-    va.idx = bs.v_idx;
-    va.idx_s = bs.v_idx2;
-    va.flag = bs.v_flag;
-    va.vid1 = bs.v_vid;
-    va.cfirst = bs.v_cfirst;
-    va.clast = bs.v_clast;
-    va.cmeta = bs.v_cmeta;
-    va.cent = bs.v_cent;
-    va.cnt = bs.v_cnt;
-    va.tmp = bs.v_tmp;
-    va.tmp_bytes = tmp_bytes;
+    voxel_scratch(bs, va, true, st);
     va.out_xyz = d_out;
-    va.out_cnt = bs.v_ocnt;
-    va.res = bs.v_res;
     HIPCHK(launch_voxel(va, st));
     unsigned long long res[kVoxelRes];
     HIPCHK(hipMemcpyAsync(res, bs.v_res, sizeof res, hipMemcpyDeviceToHost, st));
@@ -967,6 +1010,65 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
             std::fprintf(stderr, "[gicp] cloud n=%lld tiles=%d (%.2fx min) extent cap=%d cells rho=%.4f | ms:%s\n",
                          (long long)n, cl.ntiles, cl.ntiles / std::ceil(n / 64.0), cl.level, cl.rho, tlog.c_str());
     }
+}
+
+// One insert into the local voxel map: the n points in mp.pts ([n][dim], device, original row
+// order, sensor frame) are moved by T (sensor -> world, (dim+1)^2 row-major), the window is re-centred on T's
+// translation, and rows and points are merged into the map's other buffer.  One stream sync; only the result
+// words return to the host.
+void map_insert_core(VoxelMap& mp, BuildScratch& bs, int64_t n, const double* T, hipStream_t st) {
+    const int d = mp.dim;
+    for (int k = 0; k < (d + 1) * (d + 1); ++k)
+        if (!std::isfinite(T[k])) throw Fail{GICP_E_INVALID, "T contains non-finite values"};
+    if (mp.rows + n > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "map and scan together hold more than 2^31 rows"};
+    MapArgs ma{};
+    for (int a = 0; a < d; ++a) {
+        for (int b = 0; b < d; ++b) ma.R[a * 3 + b] = T[a * (d + 1) + b];
+        ma.t[a] = T[a * (d + 1) + d];
+        const double c = std::floor(ma.t[a] / mp.leaf);   // the centre cell
+        if (!(std::fabs(c) + (double)mp.R < 2147483648.0)) {
+            char b[160];
+            std::snprintf(b, sizeof b, "map window leaves the int32 cell range: axis %d is centred on cell %.6g with a half-width of %lld cells",
+                          a, c, (long long)mp.R);
+            throw Fail{GICP_E_INVALID, b};
+        }
+        ma.lo[a] = (int64_t)c - mp.R;
+    }
+    const int64_t N = mp.rows + n;
+    const int nb = mp.cur ^ 1;
+    dreserve(mp.cells[nb], mp.cap_cells[nb], (size_t)N * 3);
+    dreserve(mp.sums[nb], mp.cap_sums[nb], (size_t)N * 4);
+    dreserve(mp.vals, mp.cap_vals, (size_t)N * 4);
+    VoxelArgs va{};
+    va.n = N;
+    va.dim = d;
+    va.min_points = 1;
+    va.leaf = mp.leaf;
+    va.end_bit = std::max(1, d * mp.bits);
+    voxel_scratch(bs, va, false, st);
+    ma.cells_old = mp.cells[mp.cur];
+    ma.sums_old = mp.sums[mp.cur];
+    ma.m_old = mp.rows;
+    ma.pts = mp.pts;
+    ma.n = n;
+    ma.dim = d;
+    ma.leaf = mp.leaf;
+    ma.span = 2 * mp.R;
+    ma.bits = mp.bits;
+    ma.vals = mp.vals;
+    ma.cells_new = mp.cells[nb];
+    ma.sums_new = mp.sums[nb];
+    HIPCHK(launch_map_insert(va, ma, st));
+    unsigned long long res[kVoxelRes];
+    HIPCHK(hipMemcpyAsync(res, bs.v_res, sizeof res, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    mp.rows = (int64_t)res[6];
+    mp.cur = nb;
+}
+
+VoxelMap& need_map(gicp_ctx* c) {
+    if (!c->map.set) throw Fail{GICP_E_STATE, "no map: call gicp_map_reset first"};
+    return c->map;
 }
 
 // Per-source-tile state that refers to target tiles (hints, candidate lists, heavy schedule):
@@ -1402,6 +1504,7 @@ void gicp_destroy(gicp_ctx* c) {
     dfree(c->d_list_rcert);
     dfree(c->d_poses);
     c->bs.release();
+    c->map.release();
     for (auto& g : c->stg) {
         g.bs.release();
         g.cl.release();
@@ -2203,6 +2306,153 @@ int gicp_get_points(gicp_ctx* c, int which, double* out) {
         HIPCHK(launch_points_out(cl.xyz64, cl.perm, cl.n, cl.dim, c->d_rot, c->stream));
         HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+int gicp_map_reset(gicp_ctx* c, int dim, double leaf, double max_range) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_map_reset", [&] {
+        if (dim != 2 && dim != 3) throw Fail{GICP_E_INVALID, "dim must be 2 or 3"};
+        if (!std::isfinite(leaf) || leaf <= 0.0) throw Fail{GICP_E_INVALID, "leaf must be finite and > 0"};
+        if (!std::isfinite(max_range) || max_range <= 0.0) throw Fail{GICP_E_INVALID, "max_range must be finite and > 0"};
+        const double R = std::ceil(max_range / leaf);
+        const double lim = dim == 3 ? 2097152.0 : 2147483648.0;   // 2^21, 2^31 cells per axis (the filter's limits)
+        if (!(2.0 * R + 1.0 <= lim)) {
+            char b[160];
+            std::snprintf(b, sizeof b, "map window too wide: %.6g cells of leaf %g per axis (at most 2^%d per axis in %d-D)",
+                          2.0 * R + 1.0, leaf, dim == 3 ? 21 : 31, dim);
+            throw Fail{GICP_E_INVALID, b};
+        }
+        VoxelMap& mp = c->map;   // (buffers are kept: grow-only)
+        mp.set = true;
+        mp.dim = dim;
+        mp.leaf = leaf;
+        mp.R = (int64_t)R;
+        uint64_t r = (uint64_t)(2 * mp.R);
+        mp.bits = 0;
+        while (r) ++mp.bits, r >>= 1;
+        mp.rows = 0;
+    });
+}
+
+int gicp_map_insert(gicp_ctx* c, int which, const double* T) {
+    if (!c || !T || (which != 0 && which != 1)) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_map_insert", [&] {
+        VoxelMap& mp = need_map(c);
+        Cloud& cl = which == 0 ? c->tgt : c->src;
+        if (!cl.n) throw Fail{GICP_E_STATE, "cloud not set"};
+        if (cl.dim != mp.dim) throw Fail{GICP_E_INVALID, "the cloud's dimension differs from the map's"};
+        dreserve(mp.pts, mp.cap_pts, (size_t)cl.n * cl.dim);
+        HIPCHK(launch_points_out(cl.xyz64, cl.perm, cl.n, cl.dim, mp.pts, c->stream));
+        map_insert_core(mp, c->bs, cl.n, T, c->stream);
+    });
+}
+
+int gicp_map_insert_points(gicp_ctx* c, const double* xyz, int64_t n, int dim, const double* T) {
+    if (!c || !T) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_map_insert_points", [&] {
+        VoxelMap& mp = need_map(c);
+        if (!xyz || n <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
+        if (n > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cloud too large (> 2^31 points)"};
+        if (dim != mp.dim) throw Fail{GICP_E_INVALID, "the cloud's dimension differs from the map's"};
+        double mn[3], mx[3];
+        scan_bounds(xyz, n, dim, mn, mx);   // (the finiteness test)
+        dreserve(mp.pts, mp.cap_pts, (size_t)n * dim);
+        HIPCHK(hipMemcpyAsync(mp.pts, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, c->stream));
+        map_insert_core(mp, c->bs, n, T, c->stream);
+    });
+}
+
+int gicp_map_size(gicp_ctx* c, int64_t* rows) {
+    if (!c || !rows) return GICP_E_INVALID;
+    *rows = c->map.set ? c->map.rows : 0;
+    return GICP_OK;
+}
+
+int gicp_map_get(gicp_ctx* c, int32_t* cells, double* centroids, int32_t* counts) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_map_get", [&] {
+        VoxelMap& mp = need_map(c);
+        const int64_t m = mp.rows;
+        if (m == 0) return;
+        const int d = mp.dim;
+        std::vector<double> sums;
+        std::vector<int32_t> cl;
+        if (centroids || counts) {
+            sums.resize((size_t)m * 4);
+            HIPCHK(hipMemcpyAsync(sums.data(), mp.sums[mp.cur], sizeof(double) * m * 4, hipMemcpyDeviceToHost, c->stream));
+        }
+        if (cells) {
+            cl.resize((size_t)m * 3);
+            HIPCHK(hipMemcpyAsync(cl.data(), mp.cells[mp.cur], sizeof(int32_t) * m * 3, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (int64_t i = 0; i < m; ++i)
+            for (int a = 0; a < d; ++a) {
+                if (cells) cells[i * d + a] = cl[i * 3 + a];
+                if (centroids) centroids[i * d + a] = sums[i * 4 + a] / sums[i * 4 + 3];   // (correctly rounded, as the device's)
+            }
+        if (counts)
+            for (int64_t i = 0; i < m; ++i) counts[i] = (int32_t)sums[i * 4 + 3];
+    });
+}
+
+int gicp_map_to_target(gicp_ctx* c, const gicp_params* p, int min_points) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_map_to_target", [&] {
+        VoxelMap& mp = need_map(c);
+        if (min_points < 1) throw Fail{GICP_E_INVALID, "min_points must be >= 1"};
+        if (mp.rows <= 0) throw Fail{GICP_E_INVALID, "the map is empty"};
+        const int dim = mp.dim;
+        const int64_t m = mp.rows;
+        BuildScratch& bs = c->bs;
+        hipStream_t st = c->stream;
+        const bool verbose = std::getenv("GICP_VERBOSE") && std::getenv("GICP_VERBOSE")[0] == '1';
+        auto tprev = std::chrono::steady_clock::now();
+        std::string tlog;
+        const std::function<void(const char*)> tick = [&](const char* what) {
+            if (!verbose) return;
+            HIPCHK(hipStreamSynchronize(st));
+            const auto t = std::chrono::steady_clock::now();
+            char b[64];
+            std::snprintf(b, sizeof b, " %s %.1f", what, std::chrono::duration<double, std::milli>(t - tprev).count());
+            tlog += b;
+            tprev = t;
+        };
+        dreserve(bs.s_in, bs.cap_in, (size_t)m * dim);
+        dreserve(bs.v_flag, bs.cap_vflag, (size_t)m);
+        dreserve(bs.v_idx, bs.cap_vidx, (size_t)m);
+        if (!bs.v_res) dalloc(bs.v_res, (size_t)kVoxelRes);
+        size_t tmp_bytes = 0;
+        HIPCHK(voxel_temp_bytes(m, 1, &tmp_bytes, st));
+        dreserve(bs.v_tmp, bs.cap_vtmp, tmp_bytes + 16);
+        HIPCHK(launch_map_centroids(mp.sums[mp.cur], m, dim, min_points, bs.v_flag, bs.v_idx, bs.v_tmp, tmp_bytes, bs.s_in,
+                                    bs.v_res, st));
+        unsigned long long res[kVoxelRes];
+        HIPCHK(hipMemcpyAsync(res, bs.v_res, sizeof res, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const int64_t M = (int64_t)res[6];
+        if (M <= 0) {
+            char b[128];
+            std::snprintf(b, sizeof b, "map: none of the %lld voxels holds min_points = %d points", (long long)m, min_points);
+            throw Fail{GICP_E_INVALID, b};
+        }
+        double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+        for (int a = 0; a < dim; ++a) {
+            mn[a] = dec_ordered(res[a]);
+            mx[a] = dec_ordered(res[3 + a]);
+        }
+        tick("map-centroids");
+        c->ptgt = resolve(dim, p);
+        c->top_ready = false;
+        Cloud& cl = c->tgt;
+        cl.n = 0;   // buffers are kept (grow-only) and reused
+        cl.cov_ready = false;
+        cl.graph_ready = false;
+        cl.dim = dim;
+        cl.bits = dim == 3 ? 10 : 16;
+        build_core(cl, M, dim, mn, mx, c->ptgt, c->use_graph && c->use_certs, bs, st, false, 0, 1, kTile, tick, verbose, tlog);
+        if (c->src.n) reset_tile_state(c);
     });
 }
 

@@ -328,6 +328,30 @@ struct VoxelArgs {
     unsigned long long* res;  // [kVoxelRes]
 };
 
+// Local voxel map (gicp_voxel.hip): rows (cell, coordinate sums, count) of the filter's absolute
+// grid in ascending lexicographic order of the cells, kept inside a cube window of 2 R + 1 cells per axis.  One
+// insert sorts the map's rows (0 .. m_old - 1) and the posed scan's points (m_old .. m_old + n - 1) together by
+// the cell relative to the window's lowest corner, `bits` bits per axis, x most significant; a row outside the
+// window takes the key kMapInvalid, which no row inside it can have (2 R + 1 is odd, so the x field of a valid
+// key is never all ones; R = 0 sorts on one bit, which only the invalid key sets).
+constexpr uint64_t kMapInvalid = ~0ull;
+struct MapArgs {
+    const int32_t* cells_old; // [m_old][3] the map's rows before the insert
+    const double* sums_old;   // [m_old][4] sum x, y, z of the merged points and their number (an exact integer)
+    int64_t m_old;
+    const double* pts;        // [n][dim] the scan in its original row order, sensor frame
+    int64_t n;
+    int32_t dim;
+    double leaf;
+    double R[9], t[3];        // sensor -> world (R[a * 3 + b]; 2-D uses a, b < 2)
+    int64_t lo[3];            // the window's lowest cell per axis
+    int64_t span;             // 2 R: the highest relative cell
+    int32_t bits;             // key bits per axis (0 when R = 0)
+    double* vals;             // [m_old + n][4] staged rows: (sx, sy, sz, count) or (x, y, z, 1)
+    int32_t* cells_new;       // [rows][3] out
+    double* sums_new;         // [m_old + n][4] out (the row after the last valid one takes the dropped rows' sum)
+};
+
 constexpr int nstat(int D) {
     return (D * (D + 1) / 2) * (D * (D + 1) / 2) + (D * (D + 1) / 2) * D + (D * (D + 1) / 2) + D * D + D + 2;
 }

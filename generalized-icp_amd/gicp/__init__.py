@@ -117,6 +117,7 @@ class Engine:
         self._hook = None          # keeps the ctypes callback of set_allreduce alive
         self._hook_fn = None       # (fn, nranks, rank) of that hook, to restore it after a gicp() call
         self.voxel = (0.0, 1)      # (voxel_size, min_points) of set_voxel; size 0: no filter
+        self.map_dim = None        # dimension of the local voxel map (map_reset)
 
     def close(self):
         if self._ctx:
@@ -268,6 +269,60 @@ class Engine:
         check(self._lib.gicp_get_points(self._ctx, 0 if which == "target" else 1, dptr(out)), self._ctx,
               "gicp_get_points")
         return out
+
+    # ---- local voxel map (gicp_map_*) ----
+    def map_reset(self, voxel_size, max_range, dim=None):
+        """Create or empty the engine's local voxel map (gicp_map_reset): voxels of the absolute grid
+        floor(x / voxel_size) in the world frame, kept within ceil(max_range / voxel_size) cells of the last
+        inserted pose's cell on every axis.  dim defaults to the engine's clouds' dimension (3 before any)."""
+        d = int(dim if dim is not None else (self.dim or 3))
+        check(self._lib.gicp_map_reset(self._ctx, d, float(voxel_size), float(max_range)), self._ctx, "gicp_map_reset")
+        self.map_dim = d
+
+    def map_insert(self, T=None, which="source", points=None):
+        """Merge a cloud posed at T (sensor -> world, identity if None) into the map: the engine's indexed
+        `which` cloud straight from the device (with set_voxel in force, the filtered cloud), or the host
+        array `points`.  The window is re-centred on T's translation; what leaves it is forgotten."""
+        d = self.map_dim or self.dim or 3
+        T = np.eye(d + 1) if T is None else np.ascontiguousarray(np.asarray(T, dtype=np.float64))
+        if points is not None:
+            a = self._cloud(points)
+            if T.shape != (a.shape[1] + 1,) * 2:
+                raise ValueError(f"T must be {a.shape[1] + 1} x {a.shape[1] + 1}")
+            check(self._lib.gicp_map_insert_points(self._ctx, dptr(a), a.shape[0], a.shape[1], dptr(T)), self._ctx,
+                  "gicp_map_insert_points")
+            return
+        if T.shape != (d + 1, d + 1):
+            raise ValueError(f"T must be {d + 1} x {d + 1}")
+        check(self._lib.gicp_map_insert(self._ctx, 0 if which == "target" else 1, dptr(T)), self._ctx, "gicp_map_insert")
+
+    def map_size(self):
+        """Voxels the map holds (gicp_map_size)."""
+        n = C.c_int64()
+        check(self._lib.gicp_map_size(self._ctx, C.byref(n)), self._ctx, "gicp_map_size")
+        return int(n.value)
+
+    def map_get(self):
+        """The map's rows in ascending lexicographic order of the cells (gicp_map_get):
+        (cells int32 [M, d], centroids [M, d], counts int32 [M])."""
+        m = self.map_size()
+        d = self.map_dim or self.dim or 3
+        cells = np.empty((m, d), dtype=np.int32)
+        cent = np.empty((m, d))
+        cnt = np.empty(m, dtype=np.int32)
+        p32 = C.POINTER(C.c_int32)
+        check(self._lib.gicp_map_get(self._ctx, cells.ctypes.data_as(p32), dptr(cent), cnt.ctypes.data_as(p32)), self._ctx,
+              "gicp_map_get")
+        return cells, cent, cnt
+
+    def map_to_target(self, params=None, min_points=1):
+        """The centroids of the map's voxels holding at least min_points points become the target
+        (gicp_map_to_target), in the order of map_get; the source is left alone."""
+        d = self.map_dim or self.dim or 3
+        p = params or default_params(d)
+        check(self._lib.gicp_map_to_target(self._ctx, C.byref(p), int(min_points)), self._ctx, "gicp_map_to_target")
+        self.dim = d
+        self.n_tgt = self.cloud_size("target")
 
     def covariances(self, which="target"):
         w = 0 if which == "target" else 1

@@ -149,6 +149,12 @@ SIGNATURES = {
     "gicp_set_voxel": (C.c_int, [_VP, C.c_double, C.c_int]),
     "gicp_cloud_size": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64)]),
     "gicp_get_points": (C.c_int, [_VP, C.c_int, _DP]),
+    "gicp_map_reset": (C.c_int, [_VP, C.c_int, C.c_double, C.c_double]),
+    "gicp_map_insert": (C.c_int, [_VP, C.c_int, _DP]),
+    "gicp_map_insert_points": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, _DP]),
+    "gicp_map_size": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
+    "gicp_map_get": (C.c_int, [_VP, C.POINTER(C.c_int32), _DP, C.POINTER(C.c_int32)]),
+    "gicp_map_to_target": (C.c_int, [_VP, C.POINTER(Params), C.c_int]),
 }
 
 # gicp_allreduce_fn: int (*)(double* buf, int n, void* user)

@@ -14,6 +14,11 @@ previous sensor frame into the current one (p_cur = T p_prev), so the sensor pos
 T^-1: `composition='se3'` (default) is that exact SE(d) update; `composition='reference'` is the
 demo's first-order update (robot-visualization.py:257-265: translation -T[:2, d], yaw
 -atan2(T[1,0], T[0,0]), rotated by the last yaw), kept for trajectory comparisons with the demo.
+
+Scan-to-map (`map_voxel_size=...`): the engine keeps a local voxel map in the world frame
+(`Engine.map_*`); every scan is the source, registered against the map's centroids from the predicted
+sensor pose, then merged into the map at the pose found, and the map becomes the next target.  A
+registration error then moves one scan within the map instead of being integrated into every later pose.
 """
 import math
 import time
@@ -25,11 +30,25 @@ from . import Engine, default_params
 
 class Odometry:
     def __init__(self, dim=3, params=None, device=0, composition="se3", init="constant_velocity", borrow=False,
-                 voxel_size=None, voxel_min_points=1, **kw):
+                 voxel_size=None, voxel_min_points=1, map_voxel_size=None, map_range=None, map_min_points=1, **kw):
         if composition not in ("se3", "reference"):
             raise ValueError("composition must be 'se3' or 'reference'")
         if init not in ("identity", "constant_velocity"):
             raise ValueError("init must be 'identity' or 'constant_velocity'")
+        # map_voxel_size: scan-to-map mode (None: scan-to-scan).  The map's voxels have that edge, the map reaches
+        # map_range from the sensor along every axis, and voxels with fewer than map_min_points points are not
+        # registered against
+        if map_voxel_size is not None:
+            if map_range is None:
+                raise ValueError("map_voxel_size needs map_range")
+            if composition == "reference":
+                raise ValueError("composition='reference' (the demo's first-order update of scan-to-scan results) "
+                                 "has no meaning in scan-to-map mode")
+            if int(map_min_points) < 1:
+                raise ValueError("map_min_points must be >= 1")
+        self.map_voxel_size = None if map_voxel_size is None else float(map_voxel_size)
+        self.map_range = None if map_range is None else float(map_range)
+        self.map_min_points = int(map_min_points)
         self.dim = dim
         self.params = params if params is not None else default_params(dim, **kw)
         self.eng = Engine(device)
@@ -58,6 +77,9 @@ class Odometry:
             self.eng.cancel_stage()
         self._staged = []                    # the scan objects whose builds are staged, oldest first
         self.timing = {"setup_s": 0.0, "align_s": 0.0, "iterations": 0}
+        if getattr(self, "map_voxel_size", None) is not None:
+            self.eng.map_reset(self.map_voxel_size, self.map_range, dim)
+            self.timing.update(map_s=0.0, map_insert_s=0.0, map_target_s=0.0)
 
     def _prep(self, scan):
         return np.ascontiguousarray(np.asarray(scan, dtype=np.float64)[:, :self.dim])
@@ -69,7 +91,12 @@ class Odometry:
         same objects as `scan` of the next calls, in order.  By default the library copies a staged scan
         before the call returns, so the caller may reuse the array at once; with borrow=True the library
         reads the caller's array in place (no copy on this thread), and the caller must leave it unchanged
-        until that scan has itself been step()ped."""
+        until that scan has itself been step()ped.
+
+        In scan-to-map mode the scan is registered against the map and then merged into it; T is the same
+        quantity, P_k^-1 P_{k-1} of the sensor poses, and the coming scans are accepted and ignored."""
+        if getattr(self, "map_voxel_size", None) is not None:
+            return self._step_map(scan)
         t0 = time.perf_counter()
         if self._staged and self._staged[0] is scan:
             try:
@@ -105,6 +132,39 @@ class Odometry:
         self.timing["iterations"] += res["iterations"]
         self.last_T = T
         self._integrate(T)
+        return T, res
+
+    def _step_map(self, scan):
+        t0 = time.perf_counter()
+        eng = self.eng
+        eng.set_source(self._prep(scan), self.params)
+        t1 = time.perf_counter()
+        self.timing["setup_s"] += t1 - t0
+        self.frames += 1
+        T = res = None
+        if self.frames == 1:
+            P = self.pose
+        else:
+            prev = self._poses[-1]
+            pred = prev
+            if self.init == "constant_velocity" and len(self._poses) >= 2:
+                pred = prev @ (np.linalg.inv(self._poses[-2]) @ prev)
+            P, res = eng.align(pred, self.params)      # source -> target = sensor -> world
+            t2 = time.perf_counter()
+            self.timing["align_s"] += t2 - t1
+            self.timing["iterations"] += res["iterations"]
+            T = np.linalg.inv(P) @ prev
+            self.last_T = T
+            self._pose = P
+            self._poses.append(P.copy())
+            t1 = t2
+        eng.map_insert(P, which="source")
+        t2 = time.perf_counter()
+        eng.map_to_target(self.params, self.map_min_points)
+        t3 = time.perf_counter()
+        self.timing["map_insert_s"] += t2 - t1
+        self.timing["map_target_s"] += t3 - t2
+        self.timing["map_s"] += t3 - t1
         return T, res
 
     def run(self, scans, depth=2):

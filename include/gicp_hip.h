@@ -343,6 +343,45 @@ int gicp_set_voxel(gicp_ctx* ctx, double leaf, int min_points);
 int gicp_cloud_size(gicp_ctx* ctx, int which, int64_t* n);      /* points the indexed cloud holds (0: not set) */
 int gicp_get_points(gicp_ctx* ctx, int which, double* out);     /* [n][dim], the cloud's original order */
 
+/* ---- local voxel map ----------------------------------------------------------------
+ * A device-resident set of voxels of the same absolute grid as the filter above, in the WORLD frame: each
+ * holds its integer cell (int32 per axis), the fp64 sums of the coordinates of every point ever merged into
+ * it, and their int32 number; its centroid is sum / count (one correctly rounded division), computed when
+ * the map is read or made the target.  The map lives inside a cube window of |cell_a - c_a| <= R cells per
+ * axis, R = ceil(max_range / leaf), re-centred by every insert.
+ *
+ * An insert takes T = sensor -> world, (dim+1)^2 row-major, and
+ *   1. moves every point to the world frame as ((R_a0 x + R_a1 y) + R_a2 z) + t_a, each product and sum
+ *      rounded on its own (no FMA; the z term is dropped in 2-D), so NumPy's
+ *      R[a,0]*x + R[a,1]*y + R[a,2]*z + t[a] gives the same bits;
+ *   2. re-centres the window on the cell c = floor(t_a / leaf): voxels outside it are dropped and forgotten
+ *      (a region entered again starts from count 0), new points outside it are discarded;
+ *   3. merges the new points into the voxels inside it: a voxel's new sum is its stored sum first, then its
+ *      new points in the scan's row order, added in a tree that depends on their sorted positions alone (no
+ *      floating-point atomics: the same inserts give the same bits on every call, context and GPU);
+ *   4. keeps the rows in ascending lexicographic order of their cells.
+ * One stream synchronisation per insert; only a few result words return to the host.
+ *
+ * gicp_map_reset creates or empties the map.  GICP_E_INVALID for a dim other than 2 or 3, a leaf or
+ * max_range that is not finite and > 0, and a window of more than 2^21 (3-D) / 2^31 (2-D) cells per axis.
+ * gicp_map_insert merges the context's target (which = 0) or source (1) cloud as it is indexed -- with
+ * gicp_set_voxel in force, the filtered cloud -- without host traffic; gicp_map_insert_points a host cloud.
+ * GICP_E_STATE before gicp_map_reset or for a cloud that is not set; GICP_E_INVALID for a T or points that are
+ * not finite, a dimension other than the map's, and a window that would leave the int32 cell range
+ * (|c_a| + R >= 2^31; the message names the axis).
+ * gicp_map_get copies the rows out in key order: cells [rows][dim], centroids [rows][dim], counts [rows];
+ * any may be NULL.
+ * gicp_map_to_target makes the centroids of the voxels holding >= min_points points, in key order, the
+ * target cloud (index, covariances and graph built as by gicp_set_target, no host copy of the points).  It
+ * leaves the source and any staged targets alone and resets the pose-dependent caches.  GICP_E_INVALID for
+ * min_points < 1, an empty map, and when no voxel reaches min_points (the target is then unchanged). */
+int gicp_map_reset(gicp_ctx* ctx, int dim, double leaf, double max_range);
+int gicp_map_insert(gicp_ctx* ctx, int which, const double* T);
+int gicp_map_insert_points(gicp_ctx* ctx, const double* xyz, int64_t n, int dim, const double* T);
+int gicp_map_size(gicp_ctx* ctx, int64_t* rows);                /* 0 before gicp_map_reset */
+int gicp_map_get(gicp_ctx* ctx, int32_t* cells, double* centroids, int32_t* counts);
+int gicp_map_to_target(gicp_ctx* ctx, const gicp_params* p, int min_points);
+
 #ifdef __cplusplus
 }
 #endif

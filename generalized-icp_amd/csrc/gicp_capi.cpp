@@ -865,6 +865,18 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
 void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
                 bool graph, BuildScratch& bs, hipStream_t st, bool staged, int cov_shard, int cov_nshards, int tile_points,
                 const std::function<void(const char*)>& tick, bool verbose, std::string& tlog) {
+    // a build that fails part-way (an unsupported k_neighbors, a HIP error) leaves the cloud NOT SET: cl.n is
+    // raised below, before the covariances exist, and every entry point tells a usable cloud by cl.n alone
+    struct Unset {
+        Cloud& cl;
+        bool done = false;
+        ~Unset() {
+            if (done) return;
+            cl.n = 0;
+            cl.cov_ready = false;
+            cl.graph_ready = false;
+        }
+    } unset{cl};
     double ext = 0.0;
     for (int a = 0; a < dim; ++a) ext = std::max(ext, mx[a] - mn[a]);
     ext = ext * (1.0 + 1e-9) + 1e-12 * (1.0 + std::fabs(mn[0]));
@@ -1010,6 +1022,7 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
             std::fprintf(stderr, "[gicp] cloud n=%lld tiles=%d (%.2fx min) extent cap=%d cells rho=%.4f | ms:%s\n",
                          (long long)n, cl.ntiles, cl.ntiles / std::ceil(n / 64.0), cl.level, cl.rho, tlog.c_str());
     }
+    unset.done = true;
 }
 
 // One insert into the local voxel map: the n points in mp.pts ([n][dim], device, original row

@@ -174,7 +174,13 @@ const char* gicp_build_info(void);
 
 /* ---- clouds -------------------------------------------------------------- */
 /* Target cloud (gicp.py:101,104): builds the tile index and the per-point
- * surface covariances once; reusable across gicp_align calls. */
+ * surface covariances once; reusable across gicp_align calls.
+ * A failed build leaves no half-built cloud: after gicp_set_target, gicp_set_source or gicp_map_to_target
+ * has failed once the build of the cloud began (non-finite coordinates, an unsupported k_neighbors, a HIP
+ * error), that cloud is NOT SET -- gicp_cloud_size gives 0, and gicp_iterate, gicp_align,
+ * gicp_get_covariances, gicp_get_neighbor_counts and gicp_get_graph report GICP_E_STATE -- until a later
+ * build of it succeeds; the other cloud is untouched, and results after the good rebuild are those of a
+ * fresh context.  (A call refused for its arguments before the build began leaves the cloud as it was.) */
 int gicp_set_target(gicp_ctx* ctx, const double* xyz, int64_t M, int dim, const gicp_params* p);
 /* Source cloud (gicp.py:100,111): the whole cloud is uploaded and indexed (its
  * covariance neighbourhoods need every point); this rank reduces only the
@@ -264,7 +270,11 @@ int gicp_cg_inner_2d(const double* stats, const double* T_k, const double* x0, d
                      int32_t* counts);
 
 /* The whole outer loop (gicp.py:116-167) on the GPU: per iteration the correspondence pass
- * (k_corr), the statistics exchange when sharded, the pose solve + convergence test (k_solve). */
+ * (k_corr), the statistics exchange when sharded, the pose solve + convergence test (k_solve).
+ * T0 = NULL starts at the identity; p = NULL means the parameters the source was set with.  The
+ * max_distance_correspondence and cov_model of the last gicp_align stay in force for later gicp_iterate
+ * calls, until the next build of the source cloud (gicp_set_source, gicp_target_to_source,
+ * gicp_commit_target) brings its own; caches built under the old values change no result. */
 int gicp_align(gicp_ctx* ctx, const double* T0, const gicp_params* p, double* T_out, gicp_result* res);
 
 /* What the drop-in's 7-tuple needs from each iteration of that loop (gicp.py:108,121,154,167-172),

@@ -520,6 +520,10 @@ gicp_params resolve(int dim, const gicp_params* in) {
     if (p.epsilon == 0.0) p.epsilon = 100.0;
     if (p.cov_model < GICP_COV_PLANE_TO_PLANE || p.cov_model > GICP_COV_POINT_TO_PLANE)
         throw Fail{GICP_E_INVALID, "cov_model must be GICP_COV_PLANE_TO_PLANE, _POINT_TO_POINT or _POINT_TO_PLANE"};
+    if (p.robust_kernel < GICP_ROBUST_NONE || p.robust_kernel > GICP_ROBUST_TUKEY)
+        throw Fail{GICP_E_INVALID, "robust_kernel must be GICP_ROBUST_NONE, _HUBER, _CAUCHY, _GEMAN_MCCLURE or _TUKEY"};
+    if (p.robust_kernel != GICP_ROBUST_NONE && !(std::isfinite(p.robust_scale) && p.robust_scale > 0.0))
+        throw Fail{GICP_E_INVALID, "robust_scale must be finite and > 0 with a robust kernel"};
     if (p.rotation_epsilon <= 0.0 && p.transformation_epsilon > 0.0) p.rotation_epsilon = 1.0 - p.transformation_epsilon;
     return p;
 }
@@ -1193,6 +1197,9 @@ CorrArgs corr_args(gicp_ctx* c, int single_pass) {
     a.gap_slack = (float)std::ldexp(std::sqrt((double)a.search2) + 2.0 * c->tgt.rho + 2.0 * c->src.rho, -19);
     a.cov_model = c->psrc.cov_model;
     a.pl_inv = 1.0 / (c->ptgt.epsilon * (1.0 - c->ptgt.ratio));   // target m = sqrt(eps (1 - ratio)) n
+    a.robust_kernel = c->psrc.robust_kernel;
+    a.robust_c = c->psrc.robust_scale;   // (both unread with GICP_ROBUST_NONE)
+    a.robust_c2 = c->psrc.robust_scale * c->psrc.robust_scale;
     if (c->peer.n > 1) a.peer = c->peer;   // (the exchange's sequence number is counted on the device)
     return a;
 }
@@ -1418,7 +1425,7 @@ int guard_impl(gicp_ctx* c, const char* where, const std::function<void()>& body
 
 extern "C" {
 
-int gicp_version(void) { return 100; }
+int gicp_version(void) { return 101; }
 
 int gicp_stats_size(int dim) { return (dim == 2 || dim == 3) ? nstat(dim == 2 ? 2 : 3) : GICP_E_INVALID; }
 
@@ -1750,6 +1757,8 @@ int gicp_align_trace(gicp_ctx* c, const double* T0, const gicp_params* p, double
         gicp_params prm = p ? resolve(d, p) : c->psrc;
         c->psrc.max_distance_correspondence = prm.max_distance_correspondence;
         c->psrc.cov_model = prm.cov_model;
+        c->psrc.robust_kernel = prm.robust_kernel;
+        c->psrc.robust_scale = prm.robust_scale;
         ensure_workspace(c);
         hipStream_t st = c->stream;
         // per-iteration trace rows (gicp_trace): pose + loss from k_solve, top-k rows after k_corr
@@ -1924,7 +1933,16 @@ int gicp_align_trace(gicp_ctx* c, const double* T0, const gicp_params* p, double
             }
         }
         if (hs.solve_fail == 2) throw Fail{GICP_E_COMM, "peer exchange timed out (a rank did not arrive)"};
-        if (hs.solve_fail) throw Fail{GICP_E_INVALID, "pose solve failed (degenerate statistics)"};
+        // A robust kernel can give every correspondence w = 0 (GICP_ROBUST_TUKEY with every residual beyond c):
+        // the pass's quadratic is identically zero, the solve finds its translation block sum w W not positive
+        // definite and leaves the pose where it was.  Every pose minimises that quadratic: not an error.
+        const auto zero_weight = [&] {
+            const int NS = d * (d + 1) / 2;
+            const double* Cw = hs.stats_solved + NS * NS + NS * d;   // sum w W
+            return std::all_of(Cw, Cw + NS, [](double x) { return x == 0.0; });
+        };
+        if (hs.solve_fail && !(prm.robust_kernel != GICP_ROBUST_NONE && zero_weight()))
+            throw Fail{GICP_E_INVALID, "pose solve failed (degenerate statistics)"};
         std::memcpy(T_out, hs.T, sizeof(double) * n1 * n1);
         if (res) {
             gicp_result r;

@@ -290,6 +290,11 @@ struct CorrArgs {
     PeerArgs peer;            // n > 1: the final workgroup exchanges the statistics with its peers in-kernel
     // GICP_TAIL diagnostic build: this launch's tail record ([kTailWords] realtime stamps, 100 MHz), else null
     unsigned long long* tail;
+    // robust kernel of the pass (include/gicp_hip.h GICP_ROBUST_*): read by the k_corr<D, true>
+    // instantiations only, which launch_corr picks when robust_kernel != 0.  Last in the struct, so every
+    // other argument keeps its kernel-argument offset
+    int32_t robust_kernel;
+    double robust_c, robust_c2;   // robust_scale and its square
 };
 // GICP_TAIL record of one k_corr launch: [0] workgroup 0's start, [1] the final workgroup's partial stored,
 // then the final workgroup: [2] its group ticket won, [3] group sum stored, [4] final ticket won, [5] final

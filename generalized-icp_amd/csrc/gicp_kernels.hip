@@ -1338,7 +1338,10 @@ constexpr int kSparseGroup = GICP_SPARSE_GROUP;   // candidate tiles per round t
 // hangs the launch) and replaces `vals` by the sum over ranks in rank order -- the same bits on every
 // rank.  Returns false on a timeout (uniform over the workgroup).  System-scope stores and a system
 // release before the flags; acquire loads on the flags; the areas are uncached device memory.
-template <int NV>
+// Copy: k_corr's robust instantiations call a copy of their own.  This function and its LDS word are
+// laid out per set of kernels that reach them, so sharing one with the robust kernels changed the plain
+// kernels' code (registers, instruction count); with the copy they compile as they did without them.
+template <int NV, bool Copy = false>
 __device__ bool peer_exchange(const PeerArgs P, uint64_t seq, double* vals) {   // (P by value: a reference into
                                                                              // the kernel arguments made a scratch copy)
     static_assert(NV <= kPeerSlot, "an exchange slot holds the values");
@@ -1422,7 +1425,9 @@ __global__ void __launch_bounds__(64) k_peer_probe(PeerArgs P, int rounds, doubl
     }
 }
 
-template <int D>
+// Robust: the pass weights each accepted correspondence by the robust kernel's w (A.robust_kernel != 0,
+// DESIGN.md §3l).  A compile-time choice of launch_corr's, so the plain pass carries none of it.
+template <int D, bool Robust>
 __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArgs A) {
     constexpr int NSX = nstat_ext(D);
     constexpr int NSS = nstat(D);
@@ -2578,6 +2583,31 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
                     for (int b = 0; b < D; ++b) wr[a] += W[a][b] * r[b];
                     rwr += r[a] * wr[a];
                 }
+                if constexpr (Robust) {
+                    // w from e = r^T W r (include/gicp_hip.h GICP_ROBUST_*); W~ = w W from here on: the
+                    // statistics, the det and the debug weight below take it as they took W
+                    const double e = fmax(rwr, 0.0), c2 = A.robust_c2;
+                    double w;
+                    if (A.robust_kernel == GICP_ROBUST_HUBER) {
+                        const double s = sqrt(e);
+                        w = s <= A.robust_c ? 1.0 : A.robust_c / s;
+                    } else if (A.robust_kernel == GICP_ROBUST_CAUCHY) {
+                        w = 1.0 / (1.0 + e / c2);
+                    } else if (A.robust_kernel == GICP_ROBUST_GEMAN_MCCLURE) {
+                        const double g = c2 / (c2 + e);
+                        w = g * g;
+                    } else {   // GICP_ROBUST_TUKEY
+                        const double g = 1.0 - e / c2;
+                        w = e < c2 ? g * g : 0.0;
+                    }
+#pragma unroll
+                    for (int a = 0; a < D; ++a) {
+#pragma unroll
+                        for (int b = 0; b < D; ++b) W[a][b] *= w;
+                        wr[a] *= w;
+                    }
+                    rwr *= w;
+                }
             }
             if (A.dbg_index) A.dbg_index[sc.perm[i]] = on ? (int64_t)tg.perm[j] : -1;
         } else if (q.valid) {
@@ -2838,7 +2868,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
         if (threadIdx.x == 0) s_seq = seq0 + 1;
         __syncthreads();
         const uint64_t x0 = (uint64_t)wall_clock64();
-        if (!peer_exchange<NSX>(A.peer, s_seq, s_sum)) {
+        if (!peer_exchange<NSX, Robust>(A.peer, s_seq, s_sum)) {
             if (threadIdx.x == 0) {   // a peer never arrived: fail the call, later launches exit at once
                 A.state->solve_fail = 2;
                 A.state->converged = 1;
@@ -3161,8 +3191,12 @@ int corr_grid(int q_tiles, int shard, int nshards) {
 hipError_t launch_corr(const CorrArgs& a, int dim, int grid, hipStream_t st) {
     clear_foreign_error();
     if (grid <= 0) return hipSuccess;
-    if (dim == 2) hipLaunchKernelGGL(k_corr<2>, dim3(grid), dim3(64 * kCorrWaves), 0, st, a);
-    else hipLaunchKernelGGL(k_corr<3>, dim3(grid), dim3(64 * kCorrWaves), 0, st, a);
+    const dim3 g(grid), b(64 * kCorrWaves);
+    if (a.robust_kernel != GICP_ROBUST_NONE) {   // the robust kernel's weights: their own instantiations
+        if (dim == 2) hipLaunchKernelGGL((k_corr<2, true>), g, b, 0, st, a);
+        else hipLaunchKernelGGL((k_corr<3, true>), g, b, 0, st, a);
+    } else if (dim == 2) hipLaunchKernelGGL((k_corr<2, false>), g, b, 0, st, a);
+    else hipLaunchKernelGGL((k_corr<3, false>), g, b, 0, st, a);
     return hipGetLastError();
 }
 

@@ -31,13 +31,25 @@ def stats_size(dim):
 
 
 def default_params(dim, **kw):
-    """gicp_params with the reference defaults (gicp.py:5, :11, :24, :78), overridden by kw."""
+    """gicp_params with the reference defaults (gicp.py:5, :11, :24, :78), overridden by kw.
+    robust_kernel takes a name of _lib.ROBUST_KERNELS or its GICP_ROBUST_* code."""
     p = Params()
     _lib.load().gicp_default_params(dim, C.byref(p))
     for k, v in kw.items():
         if v is not None:
-            setattr(p, k, v)
+            setattr(p, k, _robust_code(v) if k == "robust_kernel" else v)
     return p
+
+
+def _robust_code(kernel):
+    """GICP_ROBUST_* code of a robust kernel given by name or by code (None: none)."""
+    if kernel is None:
+        return 0
+    if isinstance(kernel, str):
+        if kernel not in _lib.ROBUST_KERNELS:
+            raise ValueError(f"robust_kernel must be one of {sorted(_lib.ROBUST_KERNELS)}, got {kernel!r}")
+        return _lib.ROBUST_KERNELS[kernel]
+    return int(kernel)
 
 
 def _sym_pairs(d):
@@ -704,7 +716,7 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
          max_distance_nearest_neighbors=50, *, full_output=True, mode=None, inner=None, k_neighbors=None, device=0,
          devices=None, verbose=True, T0=None, method="plane_to_plane", transformation_epsilon=0.0,
          rotation_epsilon=0.0, euclidean_fitness_epsilon=0.0, mse_relative_epsilon=0.0, voxel_size=None,
-         voxel_min_points=1):
+         voxel_min_points=1, robust_kernel=None, robust_scale=None):
     """Drop-in for gicp.py:78 — returns the same 7-tuple (gicp.py:174):
 
     (T, all_transformations, initial_source_cov_matrices, target_cov_matrices,
@@ -744,14 +756,23 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
       points (voxel_downsample), and every per-point member of the 7-tuple -- the covariance arrays, the
       highest-weight points, all_source_cov_matrices -- refers to the FILTERED clouds, whose lengths
       differ from the inputs'.
+    robust_kernel / robust_scale: None (default) is plain least squares.  'huber', 'cauchy',
+      'geman_mcclure' ('gm') or 'tukey' (or the GICP_ROBUST_* code) weights every accepted
+      correspondence of a pass by the kernel's w(s / robust_scale), s = sqrt(r^T W r) the whitened residual
+      at the pass's pose (include/gicp_hip.h): iteratively re-weighted least squares, so a moved object or
+      a structure seen in one cloud only no longer pulls the pose.  robust_scale is in units of s: metres
+      for 'point_to_point', about |r . n| / sqrt(20) for 'plane_to_plane'.  mode='fast' only (either inner
+      solver, one or several devices; the default mode of a call that names a kernel); the reference has no
+      such weights, so mode='faithful' refuses it.
     """
     src = Engine._cloud(source_points)
     tgt = Engine._cloud(target_points)
     d = src.shape[1]
     if tgt.shape[1] != d:
         raise ValueError("source and target must have the same dimension")
+    robust = _robust_code(robust_kernel)
     if mode is None:
-        mode = "faithful" if d == 2 and len(src) <= FAITHFUL_MAX_POINTS else "fast"
+        mode = "faithful" if d == 2 and len(src) <= FAITHFUL_MAX_POINTS and not robust else "fast"
     if mode not in ("faithful", "fast") or (mode == "faithful" and d != 2):
         raise ValueError("mode must be 'fast', or 'faithful' for 2-D clouds")
     inner = ("cg" if d == 2 else "newton") if inner is None else inner
@@ -759,6 +780,10 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
         raise ValueError("inner must be 'newton', or 'cg' for 2-D clouds")
     if method not in _lib.COV_MODELS:
         raise ValueError(f"method must be one of {sorted(set(_lib.COV_MODELS))}")
+    if robust and mode == "faithful":
+        raise ValueError("robust_kernel needs mode='fast': mode='faithful' replays the reference, which has no such weights")
+    if robust and not (robust_scale is not None and np.isfinite(robust_scale) and robust_scale > 0):
+        raise ValueError(f"robust_scale must be finite and > 0 with a robust kernel, got {robust_scale!r}")
     devs = _devices(device, devices)
     if mode == "faithful":
         devs = devs[:1]
@@ -767,7 +792,8 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
     p = default_params(d, max_iterations=int(max_iterations), tolerance=float(tolerance),
                        max_distance_correspondence=float(max_distance_correspondence),
                        max_distance_nearest_neighbors=float(max_distance_nearest_neighbors), k_neighbors=k_neighbors,
-                       cov_model=_lib.COV_MODELS[method])
+                       cov_model=_lib.COV_MODELS[method], robust_kernel=robust,
+                       robust_scale=None if robust_scale is None else float(robust_scale))
     pcl = dict(transformation_epsilon=float(transformation_epsilon), rotation_epsilon=float(rotation_epsilon),
                euclidean_fitness_epsilon=float(euclidean_fitness_epsilon),
                mse_relative_epsilon=float(mse_relative_epsilon))

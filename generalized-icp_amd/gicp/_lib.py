@@ -29,6 +29,8 @@ GRAPH_K = 20
 
 # gicp_params.cov_model (include/gicp_hip.h GICP_COV_*)
 COV_MODELS = {"plane_to_plane": 0, "gicp": 0, "point_to_point": 1, "icp": 1, "point_to_plane": 2}
+# gicp_params.robust_kernel (GICP_ROBUST_*): the M-estimator weight of a correspondence, DESIGN.md §3l
+ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2, "geman_mcclure": 3, "gm": 3, "tukey": 4}
 # gicp_result.stop_reason (GICP_STOP_*)
 STOP_REASONS = {0: "none", 1: "loss", 2: "transform", 3: "abs_mse", 4: "rel_mse"}
 
@@ -52,6 +54,9 @@ class Params(C.Structure):
         ("rotation_epsilon", C.c_double),
         ("euclidean_fitness_epsilon", C.c_double),
         ("mse_relative_epsilon", C.c_double),
+        ("robust_kernel", C.c_int32),
+        ("pad_robust", C.c_int32),
+        ("robust_scale", C.c_double),
     ]
 
 

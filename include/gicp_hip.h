@@ -75,7 +75,35 @@ typedef struct gicp_params {
     double euclidean_fitness_epsilon;       /* > 0: stop when |MSE - previous MSE| < this, MSE = mean squared
                                                correspondence distance of the pass (presentation/main.typ:776) */
     double mse_relative_epsilon;            /* > 0: stop when |MSE - previous| / previous < this (PCL: 1e-5) */
+    /* --- robust kernel (M-estimator weights); zero = plain least squares --- */
+    int32_t robust_kernel;                  /* GICP_ROBUST_* : per-correspondence weight w of the pass */
+    int32_t pad_robust;                     /* explicit padding, ignored */
+    double robust_scale;                    /* c of the kernel, in units of the whitened residual
+                                               s = sqrt(r^T W r); finite and > 0 unless robust_kernel is 0
+                                               (then ignored) */
 } gicp_params;
+
+/* gicp_params.robust_kernel.  For an accepted correspondence of a pass at pose T_k, with r = q - (R s + t),
+ * W the weight of the pass's cov_model (all three models), e = max(r^T W r, 0), s = sqrt(e) the whitened
+ * residual and c = robust_scale, the pass uses W~ = w W wherever it used W: in the statistics A, B, C, gR,
+ * gt and c0 (c0 becomes sum w r^T W r, the surrogate the stopping rule watches), in gicp_debug.weight, and
+ * in det(W) of gicp_top_weights and the trace's top-k rows.  The correspondence itself (gicp_debug.index
+ * stays >= 0 even where GICP_ROBUST_TUKEY gives w = 0), gicp_debug.distance, the count and the sum of
+ * |r|^2 (gicp_pass_info out[3], gicp_result.mse, gicp_result.correspondences) are unchanged.  The inner
+ * solve minimises sum w_i r_i(T)^T W_i r_i(T) with the weights frozen at T_k: iteratively re-weighted
+ * least squares, one re-weighting per outer iteration.  A pass in which every w is 0 (GICP_ROBUST_TUKEY with
+ * every residual beyond c) has an identically zero quadratic: gicp_align leaves the pose where it is, with
+ * loss 0, and goes on; gicp_solve_pose on such statistics reports GICP_E_INVALID, as for any statistics whose
+ * translation block is not positive definite.
+ * c is in units of the WHITENED residual: metres for GICP_COV_POINT_TO_POINT (W = I, s = |r|); for
+ * GICP_COV_PLANE_TO_PLANE with the reference's epsilon = 100 and ratio = 0.1, about |r . n| / sqrt(20) (two
+ * aligned surfaces: the normal direction carries 1 / (2 epsilon ratio)); for GICP_COV_POINT_TO_PLANE,
+ * |r . n| (metres along the target normal). */
+#define GICP_ROBUST_NONE 0            /* w = 1 (robust_scale ignored) */
+#define GICP_ROBUST_HUBER 1           /* w = 1 if s <= c, else c / s */
+#define GICP_ROBUST_CAUCHY 2          /* w = 1 / (1 + e / c^2) */
+#define GICP_ROBUST_GEMAN_MCCLURE 3   /* w = (c^2 / (c^2 + e))^2 */
+#define GICP_ROBUST_TUKEY 4           /* w = (1 - e / c^2)^2 if e < c^2, else 0 */
 
 /* gicp_params.cov_model (the GICP paper's three instances, presentation/main.typ:446-455) */
 #define GICP_COV_PLANE_TO_PLANE 0   /* W = inv(R C_s R^T + C_t), both surface covariances (gicp.py:143-145) */
@@ -117,13 +145,15 @@ typedef struct gicp_result {
  * order, this rank's shard only (other rows untouched).  Any pointer may be NULL. */
 typedef struct gicp_debug {
     int64_t* index;      /* [N] target index of the correspondence, -1 if rejected (gicp.py:136-138) */
-    double* weight;      /* [N, dim, dim] W_i = inv(R C_s R^T + C_t), zeros if rejected (gicp.py:143-145) */
+    double* weight;      /* [N, dim, dim] W_i = inv(R C_s R^T + C_t), zeros if rejected (gicp.py:143-145);
+                            with a robust kernel w_i W_i (GICP_ROBUST_*) */
     double* distance;    /* [N] fp64 distance to the nearest target point (gicp.py:133) */
     int32_t want_top_weights;  /* 1: the pass also keeps det(W) on the device for gicp_top_weights */
 } gicp_debug;
 
 /* ---- library ------------------------------------------------------------ */
-int gicp_version(void);                          /* 100 * major + minor */
+int gicp_version(void);                          /* 100 * major + minor; 101: gicp_params grew by robust_kernel,
+                                                    pad_robust, robust_scale (appended) */
 int gicp_stats_size(int dim);                    /* 26 (dim 2) or 74 (dim 3) */
 void gicp_default_params(int dim, gicp_params* out);
 const char* gicp_strerror(int code);
@@ -272,9 +302,11 @@ int gicp_cg_inner_2d(const double* stats, const double* T_k, const double* x0, d
 /* The whole outer loop (gicp.py:116-167) on the GPU: per iteration the correspondence pass
  * (k_corr), the statistics exchange when sharded, the pose solve + convergence test (k_solve).
  * T0 = NULL starts at the identity; p = NULL means the parameters the source was set with.  The
- * max_distance_correspondence and cov_model of the last gicp_align stay in force for later gicp_iterate
- * calls, until the next build of the source cloud (gicp_set_source, gicp_target_to_source,
- * gicp_commit_target) brings its own; caches built under the old values change no result. */
+ * max_distance_correspondence, cov_model, robust_kernel and robust_scale of the last gicp_align stay in
+ * force for later gicp_iterate calls, until the next build of the source cloud (gicp_set_source,
+ * gicp_target_to_source, gicp_commit_target) brings its own; caches built under the old values change no
+ * result.  (A robust_kernel outside GICP_ROBUST_*, or one other than GICP_ROBUST_NONE with a robust_scale
+ * that is not finite and > 0, is GICP_E_INVALID here and wherever a gicp_params is taken.) */
 int gicp_align(gicp_ctx* ctx, const double* T0, const gicp_params* p, double* T_out, gicp_result* res);
 
 /* What the drop-in's 7-tuple needs from each iteration of that loop (gicp.py:108,121,154,167-172),

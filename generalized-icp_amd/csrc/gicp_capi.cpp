@@ -28,6 +28,7 @@
 
 #include "../../include/gicp_hip.h"
 #include "gicp_internal.h"
+#include "gicp_mem.h"
 
 namespace gicp {
 hipError_t launch_morton(const double*, int64_t, int, const DevCloud&, uint32_t*, int32_t*, hipStream_t);
@@ -57,11 +58,6 @@ using namespace gicp;
 
 namespace {
 
-struct Fail {
-    int code;
-    std::string msg;
-};
-
 // a failing HIP call is reported to the caller (the exception) and its error cleared from HIP's
 // per-thread last error here, so it cannot fail a later call's first launch check
 #define HIPCHK(x)                                                                                  \
@@ -78,29 +74,25 @@ inline void quiet(hipError_t e) {
     if (e != hipSuccess) (void)hipGetLastError();
 }
 
-template <class T>
-void dalloc(T*& p, size_t n) {
-    if (p) {
-        quiet(hipFree(p));
-        p = nullptr;
-    }
-    if (n == 0) n = 1;
-    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T)));
+}  // namespace
+
+// the four functions gicp_mem.h's buffers reach the runtime through
+namespace gicp {
+void* dev_alloc(size_t bytes) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    return p;
 }
-template <class T>
-void dfree(T*& p) {
-    if (p) quiet(hipFree(p));
-    p = nullptr;
+void dev_free(void* p) noexcept { quiet(hipFree(p)); }
+void* pinned_alloc(size_t bytes) {
+    void* p = nullptr;
+    HIPCHK(hipHostMalloc(&p, bytes));
+    return p;
 }
-// grow-only device buffer: reallocates (contents dropped) only when n exceeds the capacity, with
-// headroom, so a stream of similar-sized clouds allocates once
-template <class T>
-void dreserve(T*& p, size_t& cap, size_t n) {
-    if (n <= cap && p) return;
-    const size_t want = std::max<size_t>({n, (size_t)(cap * 1.125), 1});
-    dalloc(p, want);
-    cap = want;
-}
+void pinned_free(void* p) noexcept { quiet(hipHostFree(p)); }
+}  // namespace gicp
+
+namespace {
 
 // A few persistent host threads for the tiling (spawning threads per cloud costs tens of us each,
 // which a 100k-point frame of a stream cannot afford).  run(n, fn) calls fn(0 .. n-1) on the workers
@@ -176,61 +168,38 @@ struct Cloud {
     double lo[3] = {0, 0, 0};
     double scale = 1.0;
     float rho = 0.f;
-    double* xyz64 = nullptr;
-    float4* rel32 = nullptr;
-    double4* cov = nullptr;
-    int32_t* perm = nullptr;
-    int32_t* inv = nullptr;
-    int32_t* ncount = nullptr;
-    TileInfo* tiles = nullptr;
-    BlockInfo* blocks = nullptr;
-    uint32_t* tile_code = nullptr;
-    TileBox* boxes = nullptr;         // the walk's compact tile records (k_build_tiles)
-    int32_t* seed_tab = nullptr;      // Morton seed lookup (DevCloud::seed_tab), built on the host
+    // the buffers are grow-only and move with the cloud: a swap of two clouds swaps them, and the side that
+    // is then cleared (n = 0) keeps its buffers as spares for the next build
+    DevBuf<double> xyz64;
+    DevBuf<float4> rel32;
+    DevBuf<double4> cov;
+    DevBuf<int32_t> perm, inv, ncount;
+    DevBuf<TileInfo> tiles;
+    DevBuf<BlockInfo> blocks;
+    DevBuf<uint32_t> tile_code;
+    DevBuf<TileBox> boxes;            // the walk's compact tile records (k_build_tiles)
+    DevBuf<int32_t> seed_tab;         // Morton seed lookup (DevCloud::seed_tab), built on the host
     int seed_shift = 0;
-    uint4* nbq = nullptr;             // neighbour graph (targets only): packed rows (line A)
-    uint4* nbx = nullptr;             // ... their last entries
-    int32_t* nbi = nullptr;           // ... and their sorted indices
+    DevBuf<uint4> nbq;                // neighbour graph (targets only): packed rows (line A)
+    DevBuf<uint4> nbx;                // ... their last entries
+    DevBuf<int32_t> nbi;              // ... and their sorted indices
     bool graph_ready = false;
     bool cov_ready = false;
     int cov_shard = 0, cov_nshards = 1;  // whose tiles' covariances were computed (build_cloud)
 
-    size_t cap_xyz = 0, cap_rel = 0, cap_cov = 0, cap_perm = 0, cap_inv = 0, cap_cnt = 0;
-    size_t cap_tiles = 0, cap_blocks = 0, cap_tcode = 0, cap_nbq = 0, cap_nbx = 0, cap_nbi = 0, cap_boxes = 0, cap_seed = 0;
     void reserve_points(int64_t np) {
-        dreserve(xyz64, cap_xyz, (size_t)np * 4);
-        dreserve(rel32, cap_rel, (size_t)np);
-        dreserve(cov, cap_cov, (size_t)np);
-        dreserve(perm, cap_perm, (size_t)np);
-        dreserve(inv, cap_inv, (size_t)np);
-        dreserve(ncount, cap_cnt, (size_t)np);
+        xyz64.reserve((size_t)np * 4);
+        rel32.reserve((size_t)np);
+        cov.reserve((size_t)np);
+        perm.reserve((size_t)np);
+        inv.reserve((size_t)np);
+        ncount.reserve((size_t)np);
     }
     void reserve_tiles(int nt, int nb) {
-        dreserve(tiles, cap_tiles, (size_t)nt);
-        dreserve(blocks, cap_blocks, (size_t)nb + (nb + kBlockTiles - 1) / kBlockTiles);   // + super-blocks
-        dreserve(tile_code, cap_tcode, (size_t)nt);
-        dreserve(boxes, cap_boxes, (size_t)nt);
-    }
-    void release() {
-        dfree(xyz64);
-        dfree(rel32);
-        dfree(cov);
-        dfree(perm);
-        dfree(inv);
-        dfree(ncount);
-        dfree(tiles);
-        dfree(blocks);
-        dfree(tile_code);
-        dfree(boxes);
-        dfree(seed_tab);
-        dfree(nbq);
-        dfree(nbx);
-        dfree(nbi);
-        cap_xyz = cap_rel = cap_cov = cap_perm = cap_inv = cap_cnt = cap_tiles = cap_blocks = cap_tcode = 0;
-        cap_nbq = cap_nbx = cap_nbi = cap_boxes = cap_seed = 0;
-        n = 0;
-        cov_ready = false;
-        graph_ready = false;
+        tiles.reserve((size_t)nt);
+        blocks.reserve((size_t)nb + (nb + kBlockTiles - 1) / kBlockTiles);   // + super-blocks
+        tile_code.reserve((size_t)nt);
+        boxes.reserve((size_t)nt);
     }
     DevCloud view() const {
         DevCloud v{};
@@ -244,9 +213,9 @@ struct Cloud {
         v.boxes = boxes;
         v.seed_tab = seed_tab;
         v.seed_shift = seed_shift;
-        v.nbq = graph_ready ? nbq : nullptr;
-        v.nbx = graph_ready ? nbx : nullptr;
-        v.nbi = graph_ready ? nbi : nullptr;
+        v.nbq = graph_ready ? nbq.get() : nullptr;
+        v.nbx = graph_ready ? nbx.get() : nullptr;
+        v.nbi = graph_ready ? nbi.get() : nullptr;
         v.n = n;
         v.ntiles = ntiles;
         v.nblocks = nblocks;
@@ -261,28 +230,24 @@ struct Cloud {
 // Scratch of one cloud build (grow-only): the synchronous builds and the staged one (which runs on
 // its own stream and host thread while the current target is registered) each own one.
 struct BuildScratch {
-    double* s_in = nullptr;
-    uint32_t *s_codes = nullptr, *s_codes2 = nullptr;
-    int32_t* s_idx = nullptr;
-    unsigned char* s_sort = nullptr;
-    float4* g_nb = nullptr;           // graph build scratch
-    float2* g_nbh = nullptr;
-    int32_t* d_amb = nullptr;         // covariance-kernel diagnostics counter
-    size_t cap_in = 0, cap_codes = 0, cap_codes2 = 0, cap_idx = 0, cap_sort = 0, cap_gnb = 0, cap_gnbh = 0;
-    int cap_k_hint[4] = {0, 0, 0, 0};  // last tile extent-cap step per dimension (tiling warm start)
-    double* h_pinned = nullptr;       // pinned host copy of the input (staged builds)
-    size_t cap_pinned = 0;
+    DevBuf<double> s_in;
+    DevBuf<uint32_t> s_codes, s_codes2;
+    DevBuf<int32_t> s_idx;
+    DevBuf<unsigned char> s_sort;
+    DevBuf<float4> g_nb;              // graph build scratch
+    DevBuf<float2> g_nbh;
+    DevBuf<int32_t> d_amb;            // covariance-kernel diagnostics counter
+    int tile_k_hint[4] = {0, 0, 0, 0};  // last tile extent-cap step per dimension (tiling warm start)
+    PinnedBuf<double> h_pinned;       // pinned host copy of the input (staged builds)
     // voxel filter (gicp_voxel.hip): the raw cloud, keys and indices before and after the sort, head flags,
     // voxel ids, per-wave carries, per-voxel centroids and counts, the kept counts, rocPRIM scratch, results
-    double* v_raw = nullptr;
-    uint64_t *v_keys = nullptr, *v_keys2 = nullptr;
-    int32_t *v_idx = nullptr, *v_idx2 = nullptr, *v_flag = nullptr, *v_vid = nullptr, *v_cnt = nullptr, *v_ocnt = nullptr;
-    double *v_cfirst = nullptr, *v_clast = nullptr, *v_cent = nullptr;
-    int2* v_cmeta = nullptr;
-    unsigned char* v_tmp = nullptr;
-    unsigned long long* v_res = nullptr;
-    size_t cap_vraw = 0, cap_vkeys = 0, cap_vkeys2 = 0, cap_vidx = 0, cap_vidx2 = 0, cap_vflag = 0, cap_vvid = 0, cap_vcnt = 0,
-           cap_vocnt = 0, cap_vcf = 0, cap_vcl = 0, cap_vcent = 0, cap_vcm = 0, cap_vtmp = 0;
+    DevBuf<double> v_raw;
+    DevBuf<uint64_t> v_keys, v_keys2;
+    DevBuf<int32_t> v_idx, v_idx2, v_flag, v_vid, v_cnt, v_ocnt;
+    DevBuf<double> v_cfirst, v_clast, v_cent;
+    DevBuf<int2> v_cmeta;
+    DevBuf<unsigned char> v_tmp;
+    DevBuf<unsigned long long> v_res;
     std::unique_ptr<WorkerPool> pool;  // tiling threads (lazily started)
     WorkerPool& workers() {
         if (!pool) {
@@ -290,37 +255,6 @@ struct BuildScratch {
             pool.reset(new WorkerPool((int)std::min(7u, hc > 1 ? hc - 1 : 0u)));
         }
         return *pool;
-    }
-    void release() {
-        dfree(s_in);
-        dfree(s_codes);
-        dfree(s_codes2);
-        dfree(s_idx);
-        dfree(s_sort);
-        dfree(g_nb);
-        dfree(g_nbh);
-        dfree(d_amb);
-        if (h_pinned) quiet(hipHostFree(h_pinned));
-        h_pinned = nullptr;
-        dfree(v_raw);
-        dfree(v_keys);
-        dfree(v_keys2);
-        dfree(v_idx);
-        dfree(v_idx2);
-        dfree(v_flag);
-        dfree(v_vid);
-        dfree(v_cnt);
-        dfree(v_ocnt);
-        dfree(v_cfirst);
-        dfree(v_clast);
-        dfree(v_cent);
-        dfree(v_cmeta);
-        dfree(v_tmp);
-        dfree(v_res);
-        pool.reset();
-        cap_in = cap_codes = cap_codes2 = cap_idx = cap_sort = cap_gnb = cap_gnbh = cap_pinned = 0;
-        cap_vraw = cap_vkeys = cap_vkeys2 = cap_vidx = cap_vidx2 = cap_vflag = cap_vvid = cap_vcnt = cap_vocnt = 0;
-        cap_vcf = cap_vcl = cap_vcent = cap_vcm = cap_vtmp = 0;
     }
 };
 
@@ -334,23 +268,43 @@ struct VoxelMap {
     int bits = 0;                     // key bits per axis: ceil(log2(2 R + 1))
     int64_t rows = 0;
     int cur = 0;
-    int32_t* cells[2] = {nullptr, nullptr};   // [rows][3]
-    double* sums[2] = {nullptr, nullptr};     // [rows][4]
-    size_t cap_cells[2] = {0, 0}, cap_sums[2] = {0, 0};
-    double* pts = nullptr;            // [n][dim] the scan being inserted, original order
-    double* vals = nullptr;           // [rows + n][4] staged values of an insert
-    size_t cap_pts = 0, cap_vals = 0;
-    void release() {
-        for (int b = 0; b < 2; ++b) {
-            dfree(cells[b]);
-            dfree(sums[b]);
-            cap_cells[b] = cap_sums[b] = 0;
-        }
-        dfree(pts);
-        dfree(vals);
-        cap_pts = cap_vals = 0;
-        rows = 0;
-        set = false;
+    DevBuf<int32_t> cells[2];         // [rows][3]
+    DevBuf<double> sums[2];           // [rows][4]
+    DevBuf<double> pts;               // [n][dim] the scan being inserted, original order
+    DevBuf<double> vals;              // [rows + n][4] staged values of an insert
+};
+
+// How a cloud is built (build_cloud / build_core); the defaults are a plain synchronous build.
+struct BuildSpec {
+    bool graph = false;               // also the neighbour graph (targets: k_corr's graph descent)
+    bool staged = false;              // runs beside a registration: one k_knn_cov wave per tile
+    // the covariances are computed for that shard's tiles only (a sharded source: every rank needs the whole
+    // cloud's index for the neighbourhoods, but only its own tiles' covariances); the other rows read NaN
+    int cov_shard = 0, cov_nshards = 1;
+    int tile_points = kTile;          // points per tile at most (64; a source may take 32 or 16: GICP_SRC_TILE)
+    // leaf > 0: the uploaded cloud is first reduced to one centroid per voxel holding >= voxel_min points (the
+    // voxel filter, on the device), and the index is built over those centroids in key order
+    double voxel_leaf = 0.0;
+    int voxel_min = 1;
+    hipStream_t stream = nullptr;
+};
+
+// GICP_VERBOSE=1: the time of each phase of a build, printed with the cloud's figures when it is done.
+// tick() synchronises the stream, so it does nothing unless verbose.
+struct BuildLog {
+    hipStream_t st;
+    bool verbose = std::getenv("GICP_VERBOSE") && std::getenv("GICP_VERBOSE")[0] == '1';
+    std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+    std::string text;
+    explicit BuildLog(hipStream_t s) : st(s) {}
+    void tick(const char* what) {
+        if (!verbose) return;
+        HIPCHK(hipStreamSynchronize(st));
+        const auto t = std::chrono::steady_clock::now();
+        char b[64];
+        std::snprintf(b, sizeof b, " %s %.1f", what, std::chrono::duration<double, std::milli>(t - prev).count());
+        text += b;
+        prev = t;
     }
 };
 
@@ -363,40 +317,35 @@ struct gicp_ctx {
     Cloud tgt, src;
     gicp_params ptgt{}, psrc{};
     int shard = 0, nshards = 1, q_begin = 0, q_end = 0;
-    int32_t* d_hint = nullptr;
-    double* d_partials = nullptr;
-    size_t partials_cap = 0;
-    IterState* d_state = nullptr;
-    IterState* h_state = nullptr;     // pinned mirror
-    uint32_t* d_tickets = nullptr;
-    double* d_gpart = nullptr;
+    // Every device and pinned buffer below owns itself (gicp_mem.h): delete c releases them.  The reserved ones
+    // are grow-only (a frame stream allocates once); the fixed ones are allocated on first use.
+    DevBuf<int32_t> d_hint;
+    DevBuf<double> d_partials;
+    DevBuf<IterState> d_state;
+    PinnedBuf<IterState> h_state;     // pinned mirror
+    DevBuf<uint32_t> d_tickets;
+    DevBuf<double> d_gpart;
     double h_stats[80];
-    int32_t* d_amb = nullptr;
-    int64_t* d_dbg_idx = nullptr;
-    double* d_dbg_w = nullptr;
-    double* d_dbg_dist = nullptr;
-    double* d_dbg_det = nullptr;      // det(W) per source point (gicp_top_weights)
-    size_t dbg_cap = 0;
+    DevBuf<int64_t> d_dbg_idx;
+    DevBuf<double> d_dbg_w, d_dbg_dist;
+    DevBuf<double> d_dbg_det;         // det(W) per source point (gicp_top_weights)
     bool top_ready = false;           // the last pass recorded det(W)
     // the top-k of that pass, computed inside the pass (same stream sync) for k = top_k_pref, the k the
     // last gicp_top_weights call asked for: [0, 16) source, [16, 32) target indices, then 16 det values
     int top_k_pref = 5, top_cached_k = 0;
-    int64_t* h_top = nullptr;         // pinned, 32 int64 + 16 double
-    double* d_top_v = nullptr;        // top-k scratch: stage-1 candidates and outputs
-    int64_t* d_top_i = nullptr;
-    int64_t* d_top_tgt = nullptr;     // [N] sorted order: target of each correspondence (with det(W))
-    int64_t* d_top_out = nullptr;
+    PinnedBuf<int64_t> h_top;         // 32 int64 + 16 double
+    DevBuf<double> d_top_v;           // top-k scratch: stage-1 candidates and outputs
+    DevBuf<int64_t> d_top_i;
+    DevBuf<int64_t> d_top_tgt;        // [N] sorted order: target of each correspondence (with det(W))
+    DevBuf<int64_t> d_top_out;
     // per-source-tile candidate lists
-    int32_t* d_list = nullptr;
-    int32_t* d_list_len = nullptr;
-    int32_t* d_list_pass = nullptr;
-    float* d_list_rcert = nullptr;
-    double* d_poses = nullptr;
+    DevBuf<int32_t> d_list, d_list_len, d_list_pass;
+    DevBuf<float> d_list_rcert;
+    DevBuf<double> d_poses;
     // per-source-point nearest-neighbour certificates
-    int32_t* d_cert_j = nullptr;
-    float* d_cert_gap = nullptr;
-    int32_t* d_cert_pass = nullptr;
-    size_t cap_cj = 0, cap_cg = 0, cap_cp = 0;
+    DevBuf<int32_t> d_cert_j;
+    DevBuf<float> d_cert_gap;
+    DevBuf<int32_t> d_cert_pass;
     bool use_certs = true;            // GICP_NO_CERTS=1: every pass walks every lane
     bool use_graph = true;            // GICP_NO_GRAPH=1: no target neighbour graph, no graph descent
     bool fuse_solve = true;           // GICP_FUSE_SOLVE=0: the solve as its own k_solve launch even with no exchange
@@ -432,10 +381,8 @@ struct gicp_ctx {
         const double* xyz = nullptr;   // the slot's pinned copy, or the caller's buffer (GICP_STAGE_BORROW)
         int64_t M = 0;
         int dim = 0;
-        bool graph = false;
         int device = 0;
-        double voxel_leaf = 0.0;       // the context's filter setting when the build was staged
-        int voxel_min = 1;
+        BuildSpec spec;                // graph, the context's filter setting when the build was staged, this stream
         gicp_params p{};
         int rc = GICP_OK;
         std::string err;
@@ -455,7 +402,6 @@ struct gicp_ctx {
     };
     Staged stg[GICP_MAX_STAGED];
     int stg_head = 0, stg_count = 0;
-    size_t cap_hint = 0, cap_list = 0, cap_llen = 0, cap_lpass = 0, cap_lrc = 0;
     int pass = 0;
     bool use_lists = true;
     double skin_frac = 0.2;           // candidate-list skin as a fraction of d_c (GICP_SKIN)
@@ -465,27 +411,26 @@ struct gicp_ctx {
     int nranks = 1, rank = 0;
     gicp_allreduce_fn hook = nullptr;  // host statistics exchange (gicp_set_allreduce)
     void* hook_user = nullptr;
-    double* h_xchg = nullptr;         // pinned exchange buffer of the hook
+    PinnedBuf<double> h_xchg;         // exchange buffer of the hook
     // in-kernel peer exchange (gicp_peer_export / gicp_peer_init)
-    double* d_peer_area = nullptr;    // this rank's exchange area (uncached device memory, IPC-exported)
+    // This rank's exchange area: uncached device memory (hipExtMallocWithFlags) that other processes map through
+    // IPC, so it is no DevBuf.  A raw pointer, set only once the area is zeroed, with one free in gicp_destroy.
+    double* d_peer_area = nullptr;
     void* peer_open[kMaxPeers] = {};  // the peers' areas as opened here (closed by gicp_peer_close)
     PeerArgs peer{};                  // n > 1 while the peer exchange is on
-    uint64_t* d_peer_ctr = nullptr;   // the device's exchange counter (PeerArgs::ctr)
+    DevBuf<uint64_t> d_peer_ctr;      // the device's exchange counter (PeerArgs::ctr)
     double peer_timeout_s = 10.0;
-    double* d_probe = nullptr;
-    double** d_peer_ptrs = nullptr;   // device copy of the areas' addresses (PeerArgs::area)
+    DevBuf<double> d_probe;
+    DevBuf<double*> d_peer_ptrs;      // device copy of the areas' addresses (PeerArgs::area)
     std::vector<float> iter_ms;       // sampled k_corr time per iteration of the last align (-1: not sampled)
-    double* d_rot = nullptr;          // gicp_rotated_covariances output
-    size_t cap_rot = 0;
+    DevBuf<double> d_rot;             // gicp_rotated_covariances output
     // gicp_align_trace: per-iteration rows recorded on the device ([iter][(d+1)^2 + 1] pose + loss;
     // top-k rows [iter][16] source, target, det), copied out once after the loop
-    double* d_hist = nullptr;
-    size_t cap_hist = 0;
-    int64_t* d_trace_top = nullptr;   // [iter][16] source, then [iter][16] target
-    double* d_trace_det = nullptr;    // [iter][16]
-    size_t cap_ttop = 0, cap_tdet = 0;
-    unsigned long long* d_tail = nullptr;   // GICP_TAIL diagnostic build: [iter][kTailWords] (on this context's device)
-    size_t cap_tail = 0;
+    DevBuf<double> d_hist;
+    DevBuf<int64_t> d_trace_top;      // [iter][16] source, then [iter][16] target
+    DevBuf<double> d_trace_det;       // [iter][16]
+    DevBuf<unsigned long long> d_tail;     // GICP_TAIL diagnostic build: [iter][kTailWords] (on this context's device)
+    DevBuf<unsigned long long> d_stamps;   // GICP_STAMPS / GICP_TIMELINE diagnostic builds: [wave][20]
     static constexpr int kMaxBatch = 64;
     hipEvent_t ev[2 * kMaxBatch] = {};
     int batch_hint = 0;               // iterations the last converging align ran: its first batch next time
@@ -724,24 +669,24 @@ struct VoxelOut {
 void voxel_scratch(BuildScratch& bs, VoxelArgs& va, bool centroids, hipStream_t st) {
     const int64_t n = va.n;
     const size_t nw = (size_t)((n + kWave - 1) / kWave);
-    dreserve(bs.v_keys, bs.cap_vkeys, (size_t)n);
-    dreserve(bs.v_keys2, bs.cap_vkeys2, (size_t)n);
-    dreserve(bs.v_idx, bs.cap_vidx, (size_t)n);
-    dreserve(bs.v_idx2, bs.cap_vidx2, (size_t)n);
-    dreserve(bs.v_flag, bs.cap_vflag, (size_t)n);
-    dreserve(bs.v_vid, bs.cap_vvid, (size_t)n);
+    bs.v_keys.reserve((size_t)n);
+    bs.v_keys2.reserve((size_t)n);
+    bs.v_idx.reserve((size_t)n);
+    bs.v_idx2.reserve((size_t)n);
+    bs.v_flag.reserve((size_t)n);
+    bs.v_vid.reserve((size_t)n);
     if (centroids) {
-        dreserve(bs.v_cnt, bs.cap_vcnt, (size_t)n);
-        dreserve(bs.v_ocnt, bs.cap_vocnt, (size_t)n);
-        dreserve(bs.v_cent, bs.cap_vcent, (size_t)n * 3);
+        bs.v_cnt.reserve((size_t)n);
+        bs.v_ocnt.reserve((size_t)n);
+        bs.v_cent.reserve((size_t)n * 3);
     }
-    dreserve(bs.v_cfirst, bs.cap_vcf, nw * 4);
-    dreserve(bs.v_clast, bs.cap_vcl, nw * 4);
-    dreserve(bs.v_cmeta, bs.cap_vcm, nw);
-    if (!bs.v_res) dalloc(bs.v_res, (size_t)kVoxelRes);
+    bs.v_cfirst.reserve(nw * 4);
+    bs.v_clast.reserve(nw * 4);
+    bs.v_cmeta.reserve(nw);
+    if (!bs.v_res) bs.v_res.alloc((size_t)kVoxelRes);
     size_t tmp_bytes = 0;
     HIPCHK(voxel_temp_bytes(n, va.end_bit, &tmp_bytes, st));
-    dreserve(bs.v_tmp, bs.cap_vtmp, tmp_bytes + 16);
+    bs.v_tmp.reserve(tmp_bytes + 16);
     va.keys = bs.v_keys;
     va.keys_s = bs.v_keys2;
     va.idx = bs.v_idx;
@@ -813,34 +758,16 @@ VoxelOut voxel_filter(BuildScratch& bs, const double* d_raw, int64_t n, int dim,
 }
 
 void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
-                bool graph, BuildScratch& bs, hipStream_t st, bool staged, int cov_shard, int cov_nshards, int tile_points,
-                const std::function<void(const char*)>& tick, bool verbose, std::string& tlog);
+                BuildScratch& bs, const BuildSpec& spec, BuildLog& log);
 
-// cov_shard / cov_nshards: the covariances are computed for that shard's tiles only (a sharded source: every
-// rank needs the whole cloud's index for the neighbourhoods, but only its own tiles' covariances); the other
-// rows read NaN.
-// tile_points: points per tile at most (64; a source may take 32 or 16: GICP_SRC_TILE)
-// leaf > 0: the uploaded cloud is first reduced to one centroid per voxel holding >= min_points points (the
-// voxel filter, on the device), and the index is built over those centroids in key order.
-// This is the host front: the bounds and finiteness scan and the upload; build_core does the rest from the
-// device buffer bs.s_in and the bounds.
-void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_params& p, bool graph,
-                 BuildScratch& bs, hipStream_t st, bool staged = false, int cov_shard = 0, int cov_nshards = 1,
-                 int tile_points = kTile, double leaf = 0.0, int min_points = 1) {
+// The host front of a cloud build: the bounds and finiteness scan, the upload and (spec.voxel_leaf > 0) the
+// voxel filter; build_core does the rest from the device buffer bs.s_in and the bounds.
+void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_params& p, BuildScratch& bs,
+                 const BuildSpec& spec) {
     if (!xyz || n <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
     if (n > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cloud too large (> 2^31 points)"};
-    const bool verbose = std::getenv("GICP_VERBOSE") && std::getenv("GICP_VERBOSE")[0] == '1';
-    auto tprev = std::chrono::steady_clock::now();
-    std::string tlog;
-    const std::function<void(const char*)> tick = [&](const char* what) {
-        if (!verbose) return;
-        HIPCHK(hipStreamSynchronize(st));
-        const auto t = std::chrono::steady_clock::now();
-        char b[64];
-        std::snprintf(b, sizeof b, " %s %.1f", what, std::chrono::duration<double, std::milli>(t - tprev).count());
-        tlog += b;
-        tprev = t;
-    };
+    hipStream_t st = spec.stream;
+    BuildLog log(st);
     cl.n = 0;   // buffers are kept (grow-only) and reused
     cl.cov_ready = false;
     cl.graph_ready = false;
@@ -848,27 +775,29 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
     cl.bits = dim == 3 ? 10 : 16;
     double mn[3], mx[3];
     scan_bounds(xyz, n, dim, mn, mx);
-    tick("host-scan");
-    dreserve(bs.s_in, bs.cap_in, (size_t)n * dim);
+    log.tick("host-scan");
+    bs.s_in.reserve((size_t)n * dim);
     // (a staged build passes its pinned copy: the H2D copy is then asynchronous)
-    if (leaf > 0.0) {
-        dreserve(bs.v_raw, bs.cap_vraw, (size_t)n * dim);
+    if (spec.voxel_leaf > 0.0) {
+        bs.v_raw.reserve((size_t)n * dim);
         HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
-        const VoxelOut vo = voxel_filter(bs, bs.v_raw, n, dim, mn, mx, leaf, min_points, bs.s_in, st);
+        const VoxelOut vo = voxel_filter(bs, bs.v_raw, n, dim, mn, mx, spec.voxel_leaf, spec.voxel_min, bs.s_in, st);
         n = vo.M;
         for (int a = 0; a < 3; ++a) mn[a] = vo.mn[a], mx[a] = vo.mx[a];
-        tick("voxel");
+        log.tick("voxel");
     } else {
         HIPCHK(hipMemcpyAsync(bs.s_in, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
     }
-    build_core(cl, n, dim, mn, mx, p, graph, bs, st, staged, cov_shard, cov_nshards, tile_points, tick, verbose, tlog);
+    build_core(cl, n, dim, mn, mx, p, bs, spec, log);
 }
 
 // The core of a cloud build: the n points in bs.s_in ([n][dim], device) with bounds mn / mx -> Morton sort,
 // tiles, blocks, covariances and (graph) the neighbour graph.
 void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
-                bool graph, BuildScratch& bs, hipStream_t st, bool staged, int cov_shard, int cov_nshards, int tile_points,
-                const std::function<void(const char*)>& tick, bool verbose, std::string& tlog) {
+                BuildScratch& bs, const BuildSpec& spec, BuildLog& log) {
+    hipStream_t st = spec.stream;
+    const bool graph = spec.graph;
+    const int tile_points = spec.tile_points;
     // a build that fails part-way (an unsupported k_neighbors, a HIP error) leaves the cloud NOT SET: cl.n is
     // raised below, before the covariances exist, and every entry point tells a usable cloud by cl.n alone
     struct Unset {
@@ -889,37 +818,35 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
 
     {
         cl.reserve_points(n);
-        dreserve(bs.s_codes, bs.cap_codes, (size_t)n);
-        dreserve(bs.s_codes2, bs.cap_codes2, (size_t)n);
-        dreserve(bs.s_idx, bs.cap_idx, (size_t)n);
-        if (!bs.d_amb) {
-            dalloc(bs.d_amb, 4);
-            HIPCHK(hipMemsetAsync(bs.d_amb, 0, sizeof(int32_t) * 4, st));
-        }
+        bs.s_codes.reserve((size_t)n);
+        bs.s_codes2.reserve((size_t)n);
+        bs.s_idx.reserve((size_t)n);
+        if (!bs.d_amb)
+            alloc_init(bs.d_amb, 4, [&](int32_t* d) { HIPCHK(hipMemsetAsync(d, 0, sizeof(int32_t) * 4, st)); });
         double* d_in = bs.s_in;
         uint32_t *d_codes = bs.s_codes, *d_codes_s = bs.s_codes2;
-        int32_t* d_idx = bs.s_idx;
+        int32_t *d_idx = bs.s_idx, *d_perm = cl.perm;   // (raw pointers: rocPRIM deduces its iterator types)
         DevCloud fr = cl.view();
         HIPCHK(launch_morton(d_in, n, dim, fr, d_codes, d_idx, st));
         size_t tmp_bytes = 0;
         const unsigned end_bit = (unsigned)(dim * cl.bits);
-        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_codes, d_codes_s, d_idx, cl.perm, (size_t)n, 0, end_bit,
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_codes, d_codes_s, d_idx, d_perm, (size_t)n, 0, end_bit,
                                          st));
-        dreserve(bs.s_sort, bs.cap_sort, tmp_bytes + 16);
-        HIPCHK(rocprim::radix_sort_pairs((void*)bs.s_sort, tmp_bytes, d_codes, d_codes_s, d_idx, cl.perm, (size_t)n, 0,
+        bs.s_sort.reserve(tmp_bytes + 16);
+        HIPCHK(rocprim::radix_sort_pairs(bs.s_sort.get(), tmp_bytes, d_codes, d_codes_s, d_idx, d_perm, (size_t)n, 0,
                                          end_bit, st));
-        tick("upload+sort");
+        log.tick("upload+sort");
         std::vector<uint32_t> codes(n);
         HIPCHK(hipMemcpyAsync(codes.data(), d_codes_s, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
-        tick("codes-d2h");
+        log.tick("codes-d2h");
         std::vector<int32_t> tstart, tcount;
         std::vector<uint32_t> tcode;
         // (the extent-cap hint is kept for full-size tiles, the stream's case)
         build_tile_table(codes, dim, cl.bits, tstart, tcount, tcode, cl.level,
-                         tile_points == kTile ? bs.cap_k_hint[dim & 3] : 0, bs.workers(), tile_points);
-        if (tile_points == kTile) bs.cap_k_hint[dim & 3] = cl.level;
-        tick("tiling");
+                         tile_points == kTile ? bs.tile_k_hint[dim & 3] : 0, bs.workers(), tile_points);
+        if (tile_points == kTile) bs.tile_k_hint[dim & 3] = cl.level;
+        log.tick("tiling");
         cl.ntiles = (int)tstart.size();
         cl.nblocks = (cl.ntiles + kBlockTiles - 1) / kBlockTiles;
         std::vector<TileInfo> ti(cl.ntiles);
@@ -951,7 +878,7 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
                 seed[p] = t;
             }
             seed[nb] = cl.ntiles - 1;
-            dreserve(cl.seed_tab, cl.cap_seed, nb + 1);
+            cl.seed_tab.reserve(nb + 1);
             HIPCHK(hipMemcpyAsync(cl.seed_tab, seed.data(), sizeof(int32_t) * (nb + 1), hipMemcpyHostToDevice, st));
         }
         HIPCHK(launch_build_tiles(d_in, dim, cl.perm, cl.tiles, cl.boxes, cl.ntiles, cl.xyz64, cl.rel32, cl.inv, d_rho, st));
@@ -960,17 +887,17 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
         HIPCHK(hipMemcpyAsync(&rho_bits, d_rho, sizeof(unsigned), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         std::memcpy(&cl.rho, &rho_bits, sizeof(float));
-        tick("tiles");
+        log.tick("tiles");
 
         // surface covariances (gicp.py:19-35), of this rank's tiles when sharded
-        const int qb = 0, qe = shard_tile_count(cl.ntiles, cov_shard, cov_nshards);
+        const int qb = 0, qe = shard_tile_count(cl.ntiles, spec.cov_shard, spec.cov_nshards);
         CovArgs ca{};
         ca.cl = cl.view();
         ca.q_begin = qb;
         ca.q_end = qe;
-        ca.sh_n = cov_nshards;
-        ca.sh_r = cov_shard;
-        if (cov_nshards > 1) HIPCHK(hipMemsetAsync(cl.cov, 0xFF, sizeof(double4) * n, st));   // NaN: not computed
+        ca.sh_n = spec.cov_nshards;
+        ca.sh_r = spec.cov_shard;
+        if (spec.cov_nshards > 1) HIPCHK(hipMemsetAsync(cl.cov, 0xFF, sizeof(double4) * n, st));   // NaN: not computed
         const double dn = p.max_distance_nearest_neighbors;
         ca.mg = make_margin(dim, cl.rho, cl.rho, dn);
         ca.search2 = screen_bound(ca.mg, dn);
@@ -989,16 +916,16 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
             const char* e = std::getenv("GICP_BUILD_SPLIT");
             return e ? std::atoi(e) : 0;
         }();
-        ca.split = split_env == 1 || split_env == kSub ? split_env : (!staged && cl.ntiles <= 8192 ? kSub : 1);
+        ca.split = split_env == 1 || split_env == kSub ? split_env : (!spec.staged && cl.ntiles <= 8192 ? kSub : 1);
         // the target neighbour graph (k_corr's graph descent) comes out of the covariances'
         // own two walks (k_knn_cov<D, K, true>), then one pass packs the rows
         GraphArgs ga{};
         if (graph) {
-            dreserve(cl.nbq, cl.cap_nbq, (size_t)n * 8);
-            dreserve(cl.nbx, cl.cap_nbx, (size_t)n * 3);
-            dreserve(cl.nbi, cl.cap_nbi, (size_t)n * kGraphK);
-            dreserve(bs.g_nb, bs.cap_gnb, (size_t)n * kGraphK);   // unpacked rows (scratch)
-            dreserve(bs.g_nbh, bs.cap_gnbh, (size_t)n);
+            cl.nbq.reserve((size_t)n * 8);
+            cl.nbx.reserve((size_t)n * 3);
+            cl.nbi.reserve((size_t)n * kGraphK);
+            bs.g_nb.reserve((size_t)n * kGraphK);   // unpacked rows (scratch)
+            bs.g_nbh.reserve((size_t)n);
             ga.cl = cl.view();
             ga.split = ca.split;
             ga.mg = ca.mg;
@@ -1018,13 +945,13 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
         if (graph) HIPCHK(launch_graph_pack(ga, st));
         HIPCHK(hipStreamSynchronize(st));
         cl.cov_ready = true;
-        cl.cov_shard = cov_shard;
-        cl.cov_nshards = cov_nshards;
+        cl.cov_shard = spec.cov_shard;
+        cl.cov_nshards = spec.cov_nshards;
         cl.graph_ready = graph;
-        tick(graph ? "covariances+graph" : "covariances");
-        if (verbose)
+        log.tick(graph ? "covariances+graph" : "covariances");
+        if (log.verbose)
             std::fprintf(stderr, "[gicp] cloud n=%lld tiles=%d (%.2fx min) extent cap=%d cells rho=%.4f | ms:%s\n",
-                         (long long)n, cl.ntiles, cl.ntiles / std::ceil(n / 64.0), cl.level, cl.rho, tlog.c_str());
+                         (long long)n, cl.ntiles, cl.ntiles / std::ceil(n / 64.0), cl.level, cl.rho, log.text.c_str());
     }
     unset.done = true;
 }
@@ -1053,9 +980,9 @@ void map_insert_core(VoxelMap& mp, BuildScratch& bs, int64_t n, const double* T,
     }
     const int64_t N = mp.rows + n;
     const int nb = mp.cur ^ 1;
-    dreserve(mp.cells[nb], mp.cap_cells[nb], (size_t)N * 3);
-    dreserve(mp.sums[nb], mp.cap_sums[nb], (size_t)N * 4);
-    dreserve(mp.vals, mp.cap_vals, (size_t)N * 4);
+    mp.cells[nb].reserve((size_t)N * 3);
+    mp.sums[nb].reserve((size_t)N * 4);
+    mp.vals.reserve((size_t)N * 4);
     VoxelArgs va{};
     va.n = N;
     va.dim = d;
@@ -1081,6 +1008,16 @@ void map_insert_core(VoxelMap& mp, BuildScratch& bs, int64_t n, const double* T,
     HIPCHK(hipStreamSynchronize(st));
     mp.rows = (int64_t)res[6];
     mp.cur = nb;
+}
+
+// a target built on `st` under the context's settings: with the graph unless switched off, through the voxel filter
+BuildSpec target_spec(const gicp_ctx* c, hipStream_t st) {
+    BuildSpec spec;
+    spec.graph = c->use_graph && c->use_certs;
+    spec.voxel_leaf = c->voxel_leaf;
+    spec.voxel_min = c->voxel_min;
+    spec.stream = st;
+    return spec;
 }
 
 VoxelMap& need_map(gicp_ctx* c) {
@@ -1109,15 +1046,15 @@ void set_shard(gicp_ctx* c, int shard, int nshards) {
     c->q_begin = 0;   // k_corr maps this rank's units onto the cloud's (interleaved chunks)
     c->q_end = c->src.ntiles;
     const int nt = std::max(1, c->src.ntiles);
-    dreserve(c->d_hint, c->cap_hint, nt);
-    dreserve(c->d_list, c->cap_list, (size_t)nt * kListMax);
-    dreserve(c->d_list_len, c->cap_llen, nt);
-    dreserve(c->d_list_pass, c->cap_lpass, nt);
-    dreserve(c->d_list_rcert, c->cap_lrc, nt);
-    if (!c->d_poses) dalloc(c->d_poses, (size_t)kPoseRing * 12);
-    dreserve(c->d_cert_j, c->cap_cj, (size_t)std::max<int64_t>(1, c->src.n));
-    dreserve(c->d_cert_gap, c->cap_cg, (size_t)std::max<int64_t>(1, c->src.n));
-    dreserve(c->d_cert_pass, c->cap_cp, nt);
+    c->d_hint.reserve(nt);
+    c->d_list.reserve((size_t)nt * kListMax);
+    c->d_list_len.reserve(nt);
+    c->d_list_pass.reserve(nt);
+    c->d_list_rcert.reserve(nt);
+    if (!c->d_poses) c->d_poses.alloc((size_t)kPoseRing * 12);
+    c->d_cert_j.reserve((size_t)std::max<int64_t>(1, c->src.n));
+    c->d_cert_gap.reserve((size_t)std::max<int64_t>(1, c->src.n));
+    c->d_cert_pass.reserve(nt);
     reset_tile_state(c);
 }
 
@@ -1125,19 +1062,15 @@ void ensure_workspace(gicp_ctx* c) {
     const int nsx = nstat_ext(3);
     const int grid = std::max(1, corr_grid(c->src.ntiles, c->shard, c->nshards));
     if ((grid + kGroupWG - 1) / kGroupWG > kMaxGroups) throw Fail{GICP_E_INVALID, "source shard too large"};
-    const size_t need = (size_t)grid * nsx;
-    if (need > c->partials_cap) {
-        dalloc(c->d_partials, need);
-        c->partials_cap = need;
+    c->d_partials.reserve((size_t)grid * nsx);
+    // the fixed state block, each buffer on its own first use (tickets and the pinned mirror start zeroed)
+    if (!c->d_state) c->d_state.alloc(1);
+    if (!c->h_state) alloc_init(c->h_state, 1, [](IterState* h) { std::memset(h, 0, sizeof(IterState)); });
+    if (!c->d_tickets) {
+        const size_t nt = (size_t)(kMaxGroups + 1) * kTicketStride;
+        alloc_init(c->d_tickets, nt, [&](uint32_t* d) { HIPCHK(hipMemsetAsync(d, 0, sizeof(uint32_t) * nt, c->stream)); });
     }
-    if (!c->d_state) {
-        dalloc(c->d_state, 1);
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_state), sizeof(IterState)));
-        std::memset(c->h_state, 0, sizeof(IterState));
-        dalloc(c->d_tickets, (size_t)(kMaxGroups + 1) * kTicketStride);
-        HIPCHK(hipMemsetAsync(c->d_tickets, 0, sizeof(uint32_t) * (kMaxGroups + 1) * kTicketStride, c->stream));
-        dalloc(c->d_gpart, (size_t)kMaxGroups * nsx);
-    }
+    if (!c->d_gpart) c->d_gpart.alloc((size_t)kMaxGroups * nsx);
 }
 
 // The largest double x with sqrt(x) <= dc (sqrt correctly rounded, as on the device), so the accept
@@ -1276,31 +1209,26 @@ void print_stamps(const unsigned long long* d_stamps, size_t nst) {
 // per-point debug outputs of a pass (gicp_debug) and the det(W) record of the top-k, grow-only
 void ensure_dbg(gicp_ctx* c) {
     const size_t n = (size_t)c->src.n;
-    if (c->dbg_cap < n) {
-        dalloc(c->d_dbg_idx, n);
-        dalloc(c->d_dbg_w, n * 9);
-        dalloc(c->d_dbg_dist, n);
-        dalloc(c->d_dbg_det, n);
-        dalloc(c->d_top_tgt, n);
-        c->dbg_cap = n;
-    }
+    c->d_dbg_idx.reserve(n);
+    c->d_dbg_w.reserve(n * 9);
+    c->d_dbg_dist.reserve(n);
+    c->d_dbg_det.reserve(n);
+    c->d_top_tgt.reserve(n);
 }
 
 constexpr int kTopBlocks = 256;   // stage-1 blocks of the top-k of det(W)
 
 void ensure_top_scratch(gicp_ctx* c) {
-    if (!c->d_top_v) {
-        dalloc(c->d_top_v, (size_t)kTopBlocks * 16 + 16);
-        dalloc(c->d_top_i, (size_t)kTopBlocks * 16);
-        dalloc(c->d_top_out, 32);
-    }
+    if (!c->d_top_v) c->d_top_v.alloc((size_t)kTopBlocks * 16 + 16);
+    if (!c->d_top_i) c->d_top_i.alloc((size_t)kTopBlocks * 16);
+    if (!c->d_top_out) c->d_top_out.alloc(32);
 }
 
 // Top-k of the last pass's det(W) (k_top1 / k_top2) and its copy into the pinned c->h_top, enqueued on
 // the library's stream (the caller synchronises).
 void top_enqueue(gicp_ctx* c, int k) {
     ensure_top_scratch(c);
-    if (!c->h_top) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_top), sizeof(int64_t) * 32 + sizeof(double) * 16));
+    if (!c->h_top) c->h_top.alloc(32 + 16);   // 32 int64, then 16 double
     double* ov = c->d_top_v + (size_t)kTopBlocks * 16;
     HIPCHK(launch_top_weights(c->d_dbg_det, c->d_top_tgt, c->src.perm, c->src.n, k, c->d_top_v, c->d_top_i, kTopBlocks,
                               ov, c->d_top_out, c->d_top_out + 16, c->stream));
@@ -1338,13 +1266,9 @@ void run_pass(gicp_ctx* c, const double* T, gicp_debug* dbg) {
     const int nsx = nstat_ext(d);
     const int grid = corr_grid(c->src.ntiles, c->shard, c->nshards);
 #if defined(GICP_STAMPS) || defined(GICP_TIMELINE)
-    static unsigned long long* d_stamps = nullptr;
-    static size_t stamps_cap = 0;
     const size_t nst = (size_t)std::max(1, grid) * kCorrWaves * 20;
-    if (nst > stamps_cap) {
-        dalloc(d_stamps, nst);
-        stamps_cap = nst;
-    }
+    c->d_stamps.reserve(nst);
+    unsigned long long* const d_stamps = c->d_stamps;
     HIPCHK(hipMemsetAsync(d_stamps, 0, nst * 8, st));
     a.stamps = d_stamps;
 #endif
@@ -1496,52 +1420,17 @@ void gicp_destroy(gicp_ctx* c) {
     if (c->comm) ncclCommDestroy(c->comm);
     for (auto& p : c->peer_open)
         if (p) quiet(hipIpcCloseMemHandle(p));
-    if (c->d_peer_area) quiet(hipFree(c->d_peer_area));
-    dfree(c->d_probe);
-    dfree(c->d_peer_ptrs);
-    dfree(c->d_peer_ctr);
-    c->tgt.release();
-    c->src.release();
-    dfree(c->d_hint);
-    dfree(c->d_partials);
-    dfree(c->d_state);
-    dfree(c->d_tickets);
-    dfree(c->d_gpart);
-    dfree(c->d_dbg_idx);
-    dfree(c->d_dbg_w);
-    dfree(c->d_dbg_dist);
-    dfree(c->d_dbg_det);
-    dfree(c->d_top_tgt);
-    dfree(c->d_cert_j);
-    dfree(c->d_cert_gap);
-    dfree(c->d_cert_pass);
-    dfree(c->d_top_v);
-    dfree(c->d_top_i);
-    dfree(c->d_top_out);
-    dfree(c->d_list);
-    dfree(c->d_list_len);
-    dfree(c->d_list_pass);
-    dfree(c->d_list_rcert);
-    dfree(c->d_poses);
-    c->bs.release();
-    c->map.release();
-    for (auto& g : c->stg) {
-        g.bs.release();
-        g.cl.release();
-        if (g.stream) quiet(hipStreamDestroy(g.stream));
-    }
-    if (c->h_state) quiet(hipHostFree(c->h_state));
-    if (c->h_top) quiet(hipHostFree(c->h_top));
-    if (c->h_xchg) quiet(hipHostFree(c->h_xchg));
-    dfree(c->d_rot);
-    dfree(c->d_hist);
-    dfree(c->d_trace_top);
-    dfree(c->d_trace_det);
-    dfree(c->d_tail);
+    if (c->d_peer_area) dev_free(c->d_peer_area);   // (the one buffer that is no DevBuf: see gicp_ctx)
+    // a staged build that failed may have left work enqueued on its stream (it synchronises only on success)
+    for (auto& g : c->stg)
+        if (g.stream) {
+            quiet(hipStreamSynchronize(g.stream));
+            quiet(hipStreamDestroy(g.stream));
+        }
     for (auto& e : c->ev)
         if (e) quiet(hipEventDestroy(e));
     if (c->stream) quiet(hipStreamDestroy(c->stream));
-    delete c;
+    delete c;   // every stream is idle and gone: the buffers release themselves
 }
 
 const char* gicp_last_error(const gicp_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -1604,8 +1493,7 @@ int gicp_set_target(gicp_ctx* c, const double* xyz, int64_t M, int dim, const gi
     return guard_impl(c, "gicp_set_target", [&] {
         c->ptgt = resolve(dim, p);
         c->top_ready = false;
-        build_cloud(c->tgt, xyz, M, dim, c->ptgt, c->use_graph && c->use_certs, c->bs, c->stream, false, 0, 1, kTile,
-                    c->voxel_leaf, c->voxel_min);
+        build_cloud(c->tgt, xyz, M, dim, c->ptgt, c->bs, target_spec(c, c->stream));
         if (c->src.n) reset_tile_state(c);
     });
 }
@@ -1617,8 +1505,14 @@ int gicp_set_source(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gi
         if (nshards < 1 || shard < 0 || shard >= nshards) throw Fail{GICP_E_INVALID, "bad shard / nshards"};
         c->psrc = resolve(dim, p);
         c->top_ready = false;
-        build_cloud(c->src, xyz, N, dim, c->psrc, false, c->bs, c->stream, false, shard, nshards, c->src_tile,
-                    c->voxel_leaf, c->voxel_min);
+        BuildSpec spec;
+        spec.cov_shard = shard;
+        spec.cov_nshards = nshards;
+        spec.tile_points = c->src_tile;
+        spec.voxel_leaf = c->voxel_leaf;
+        spec.voxel_min = c->voxel_min;
+        spec.stream = c->stream;
+        build_cloud(c->src, xyz, N, dim, c->psrc, c->bs, spec);
         set_shard(c, shard, nshards);
         HIPCHK(hipStreamSynchronize(c->stream));
     });
@@ -1648,7 +1542,7 @@ int gicp_get_covariances(gicp_ctx* c, int which, double* out) {
         const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
         const double I2[4] = {1, 0, 0, 1};
         const size_t m = (size_t)cl.n * d * d;
-        dreserve(c->d_rot, c->cap_rot, m);
+        c->d_rot.reserve(m);
         HIPCHK(launch_rotate_cov(cl.cov, cl.perm, cl.n, d, d == 3 ? I : I2, c->d_rot, c->stream));
         HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1769,12 +1663,12 @@ int gicp_align_trace(gicp_ctx* c, const double* T0, const gicp_params* p, double
                 throw Fail{GICP_E_INVALID, "gicp_trace.capacity < max_iterations"};
             if (tk < 0 || tk > 16) throw Fail{GICP_E_INVALID, "gicp_trace.top_k must be 0..16"};
             const size_t rows = (size_t)std::max(1, prm.max_iterations);
-            dreserve(c->d_hist, c->cap_hist, rows * HS);
+            c->d_hist.reserve(rows * HS);
             if (tk > 0) {
                 ensure_dbg(c);
                 ensure_top_scratch(c);
-                dreserve(c->d_trace_top, c->cap_ttop, rows * 32);
-                dreserve(c->d_trace_det, c->cap_tdet, rows * 16);
+                c->d_trace_top.reserve(rows * 32);
+                c->d_trace_det.reserve(rows * 16);
                 // rows of other shards stay NaN (never selected); one shard writes every row
                 if (c->nshards > 1) HIPCHK(hipMemsetAsync(c->d_dbg_det, 0xFF, sizeof(double) * c->src.n, st));
             }
@@ -1815,7 +1709,7 @@ int gicp_align_trace(gicp_ctx* c, const double* T0, const gicp_params* p, double
         const size_t ntail = (size_t)std::max(1, prm.max_iterations) * kTailWords;
         unsigned long long* d_tail = nullptr;
         if (tail_path) {   // the context's own buffer, on its device
-            dreserve(c->d_tail, c->cap_tail, ntail);
+            c->d_tail.reserve(ntail);
             d_tail = c->d_tail;
             std::vector<unsigned long long> init(ntail, 0ull);
             for (size_t k = 0; k < ntail; k += kTailWords) init[k] = ~0ull;
@@ -1995,8 +1889,7 @@ void staged_worker(gicp_ctx::Staged* gp) {
         std::string err;
         try {
             HIPCHK(hipSetDevice(gp->device));
-            build_cloud(gp->cl, gp->xyz, gp->M, gp->dim, gp->p, gp->graph, gp->bs, gp->stream, true, 0, 1, kTile,
-                        gp->voxel_leaf, gp->voxel_min);
+            build_cloud(gp->cl, gp->xyz, gp->M, gp->dim, gp->p, gp->bs, gp->spec);
         } catch (const Fail& f) {
             rc = f.code;
             err = f.msg;
@@ -2036,19 +1929,14 @@ int gicp_stage_target_ex(gicp_ctx* c, const double* xyz, int64_t M, int dim, con
         const double* src = xyz;
         if (!(flags & GICP_STAGE_BORROW)) {
             const size_t need = (size_t)M * dim;
-            if (need > g.bs.cap_pinned) {   // grow-only pinned staging buffer (allocated here, not in the worker)
-                if (g.bs.h_pinned) HIPCHK(hipHostFree(g.bs.h_pinned));
-                g.bs.h_pinned = nullptr;
-                g.bs.cap_pinned = 0;
-                const size_t cap = need + need / 8;
-                HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&g.bs.h_pinned), sizeof(double) * cap));
-                g.bs.cap_pinned = cap;
-            }
+            // grow-only pinned staging buffer (allocated here, not in the worker), with headroom from the first
+            // allocation on: need / 8
+            if (need > g.bs.h_pinned.capacity()) g.bs.h_pinned.alloc(need + need / 8);
             // the caller's scan is copied into the slot's pinned buffer before this call returns (the caller
             // may refill its buffer at once): 16 fixed chunks on the calling thread's tiling pool (a 100k-point
             // frame, 2.4 MB, in ~0.06 ms instead of one thread's ~0.3 ms)
             const size_t total = sizeof(double) * need;
-            char* dst = reinterpret_cast<char*>(g.bs.h_pinned);
+            char* dst = reinterpret_cast<char*>(g.bs.h_pinned.get());
             const char* srcb = reinterpret_cast<const char*>(xyz);
             constexpr int kChunks = 16;
             c->bs.workers().run(kChunks, [&](int k) {
@@ -2063,10 +1951,9 @@ int gicp_stage_target_ex(gicp_ctx* c, const double* xyz, int64_t M, int dim, con
             g.xyz = src;
             g.M = M;
             g.dim = dim;
-            g.graph = c->use_graph && c->use_certs;
             g.device = c->device;
-            g.voxel_leaf = c->voxel_leaf;
-            g.voxel_min = c->voxel_min;
+            g.spec = target_spec(c, g.stream);
+            g.spec.staged = true;
             g.p = prm;
             g.rc = GICP_OK;
             g.err.clear();
@@ -2143,7 +2030,7 @@ int gicp_set_allreduce_ranks(gicp_ctx* c, gicp_allreduce_fn fn, void* user, int 
     if (!c || nranks < 1 || rank < 0 || rank >= nranks) return GICP_E_INVALID;
     return guard_impl(c, "gicp_set_allreduce", [&] {
         if (fn) close_peers(c);
-        if (fn && !c->h_xchg) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->h_xchg), sizeof(double) * 80));
+        if (fn && !c->h_xchg) c->h_xchg.alloc(80);
         if (fn && c->comm) {   // one exchange per context: the hook replaces the communicator
             HIPCHK(hipStreamSynchronize(c->stream));
             ncclCommDestroy(c->comm);
@@ -2163,15 +2050,19 @@ int gicp_peer_export(gicp_ctx* c, char handle[GICP_PEER_HANDLE_BYTES]) {
     return guard_impl(c, "gicp_peer_export", [&] {
         static_assert(sizeof(hipIpcMemHandle_t) + sizeof(uint64_t) == GICP_PEER_HANDLE_BYTES, "IPC handle + counter");
         if (!c->d_peer_area) {   // uncached: peers' stores and this rank's polling meet in memory
-            HIPCHK(hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_peer_area), sizeof(double) * kPeerAreaDoubles,
+            double* area = nullptr;   // published only once it is zeroed
+            HIPCHK(hipExtMallocWithFlags(reinterpret_cast<void**>(&area), sizeof(double) * kPeerAreaDoubles,
                                          hipDeviceMallocUncached));
-            HIPCHK(hipMemset(c->d_peer_area, 0, sizeof(double) * kPeerAreaDoubles));
-            HIPCHK(hipDeviceSynchronize());
+            try {
+                HIPCHK(hipMemset(area, 0, sizeof(double) * kPeerAreaDoubles));
+                HIPCHK(hipDeviceSynchronize());
+            } catch (...) {
+                dev_free(area);
+                throw;
+            }
+            c->d_peer_area = area;
         }
-        if (!c->d_peer_ctr) {
-            dalloc(c->d_peer_ctr, 1);
-            HIPCHK(hipMemset(c->d_peer_ctr, 0, sizeof(uint64_t)));
-        }
+        if (!c->d_peer_ctr) alloc_init(c->d_peer_ctr, 1, [](uint64_t* d) { HIPCHK(hipMemset(d, 0, sizeof(uint64_t))); });
         hipIpcMemHandle_t h;
         HIPCHK(hipIpcGetMemHandle(&h, c->d_peer_area));
         uint64_t seq = 0;   // this rank's exchange counter (its launches have finished: stream sync)
@@ -2220,14 +2111,14 @@ int gicp_peer_init(gicp_ctx* c, int nranks, int rank, const char* handles, doubl
                 c->peer_open[r] = ptr;
                 area[r] = static_cast<double*>(ptr);
             }
-            if (!c->d_peer_ptrs) dalloc(c->d_peer_ptrs, kMaxPeers);
+            if (!c->d_peer_ptrs) c->d_peer_ptrs.alloc(kMaxPeers);
             HIPCHK(hipMemcpy(c->d_peer_ptrs, area, sizeof(area), hipMemcpyHostToDevice));
             p.area = c->d_peer_ptrs;
             int khz = 0;
             HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device));
             p.timeout = (uint64_t)(timeout_s * (khz > 0 ? khz : 100000) * 1e3);
             // the probe: kPeerProbeRounds full-slot exchanges checked bit for bit, which every rank runs now
-            if (!c->d_probe) dalloc(c->d_probe, 2);
+            if (!c->d_probe) c->d_probe.alloc(2);
             HIPCHK(launch_peer_probe(p, c->d_probe, c->stream));
             double got[2] = {0, 0};
             HIPCHK(hipMemcpyAsync(got, c->d_probe, sizeof(got), hipMemcpyDeviceToHost, c->stream));
@@ -2279,7 +2170,7 @@ int gicp_rotated_covariances(gicp_ctx* c, int which, const double* R, double* ou
         for (int k = 0; k < d * d; ++k)
             if (!std::isfinite(R[k])) throw Fail{GICP_E_INVALID, "R contains non-finite values"};
         const size_t m = (size_t)cl.n * d * d;
-        dreserve(c->d_rot, c->cap_rot, m);
+        c->d_rot.reserve(m);
         HIPCHK(launch_rotate_cov(cl.cov, cl.perm, cl.n, d, R, c->d_rot, c->stream));
         HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -2310,8 +2201,8 @@ int gicp_voxel_downsample(gicp_ctx* c, const double* xyz, int64_t N, int dim, do
         scan_bounds(xyz, N, dim, mn, mx);
         BuildScratch& bs = c->bs;
         hipStream_t st = c->stream;
-        dreserve(bs.v_raw, bs.cap_vraw, (size_t)N * dim);
-        dreserve(bs.s_in, bs.cap_in, (size_t)N * dim);
+        bs.v_raw.reserve((size_t)N * dim);
+        bs.s_in.reserve((size_t)N * dim);
         HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * N * dim, hipMemcpyHostToDevice, st));
         const VoxelOut vo = voxel_filter(bs, bs.v_raw, N, dim, mn, mx, leaf, min_points, bs.s_in, st);
         HIPCHK(hipMemcpyAsync(out_xyz, bs.s_in, sizeof(double) * vo.M * dim, hipMemcpyDeviceToHost, st));
@@ -2333,7 +2224,7 @@ int gicp_get_points(gicp_ctx* c, int which, double* out) {
         Cloud& cl = which == 0 ? c->tgt : c->src;
         if (!cl.n) throw Fail{GICP_E_STATE, "cloud not set"};
         const size_t m = (size_t)cl.n * cl.dim;
-        dreserve(c->d_rot, c->cap_rot, m);
+        c->d_rot.reserve(m);
         HIPCHK(launch_points_out(cl.xyz64, cl.perm, cl.n, cl.dim, c->d_rot, c->stream));
         HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -2373,7 +2264,7 @@ int gicp_map_insert(gicp_ctx* c, int which, const double* T) {
         Cloud& cl = which == 0 ? c->tgt : c->src;
         if (!cl.n) throw Fail{GICP_E_STATE, "cloud not set"};
         if (cl.dim != mp.dim) throw Fail{GICP_E_INVALID, "the cloud's dimension differs from the map's"};
-        dreserve(mp.pts, mp.cap_pts, (size_t)cl.n * cl.dim);
+        mp.pts.reserve((size_t)cl.n * cl.dim);
         HIPCHK(launch_points_out(cl.xyz64, cl.perm, cl.n, cl.dim, mp.pts, c->stream));
         map_insert_core(mp, c->bs, cl.n, T, c->stream);
     });
@@ -2388,7 +2279,7 @@ int gicp_map_insert_points(gicp_ctx* c, const double* xyz, int64_t n, int dim, c
         if (dim != mp.dim) throw Fail{GICP_E_INVALID, "the cloud's dimension differs from the map's"};
         double mn[3], mx[3];
         scan_bounds(xyz, n, dim, mn, mx);   // (the finiteness test)
-        dreserve(mp.pts, mp.cap_pts, (size_t)n * dim);
+        mp.pts.reserve((size_t)n * dim);
         HIPCHK(hipMemcpyAsync(mp.pts, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, c->stream));
         map_insert_core(mp, c->bs, n, T, c->stream);
     });
@@ -2438,25 +2329,14 @@ int gicp_map_to_target(gicp_ctx* c, const gicp_params* p, int min_points) {
         const int64_t m = mp.rows;
         BuildScratch& bs = c->bs;
         hipStream_t st = c->stream;
-        const bool verbose = std::getenv("GICP_VERBOSE") && std::getenv("GICP_VERBOSE")[0] == '1';
-        auto tprev = std::chrono::steady_clock::now();
-        std::string tlog;
-        const std::function<void(const char*)> tick = [&](const char* what) {
-            if (!verbose) return;
-            HIPCHK(hipStreamSynchronize(st));
-            const auto t = std::chrono::steady_clock::now();
-            char b[64];
-            std::snprintf(b, sizeof b, " %s %.1f", what, std::chrono::duration<double, std::milli>(t - tprev).count());
-            tlog += b;
-            tprev = t;
-        };
-        dreserve(bs.s_in, bs.cap_in, (size_t)m * dim);
-        dreserve(bs.v_flag, bs.cap_vflag, (size_t)m);
-        dreserve(bs.v_idx, bs.cap_vidx, (size_t)m);
-        if (!bs.v_res) dalloc(bs.v_res, (size_t)kVoxelRes);
+        BuildLog log(st);
+        bs.s_in.reserve((size_t)m * dim);
+        bs.v_flag.reserve((size_t)m);
+        bs.v_idx.reserve((size_t)m);
+        if (!bs.v_res) bs.v_res.alloc((size_t)kVoxelRes);
         size_t tmp_bytes = 0;
         HIPCHK(voxel_temp_bytes(m, 1, &tmp_bytes, st));
-        dreserve(bs.v_tmp, bs.cap_vtmp, tmp_bytes + 16);
+        bs.v_tmp.reserve(tmp_bytes + 16);
         HIPCHK(launch_map_centroids(mp.sums[mp.cur], m, dim, min_points, bs.v_flag, bs.v_idx, bs.v_tmp, tmp_bytes, bs.s_in,
                                     bs.v_res, st));
         unsigned long long res[kVoxelRes];
@@ -2473,7 +2353,7 @@ int gicp_map_to_target(gicp_ctx* c, const gicp_params* p, int min_points) {
             mn[a] = dec_ordered(res[a]);
             mx[a] = dec_ordered(res[3 + a]);
         }
-        tick("map-centroids");
+        log.tick("map-centroids");
         c->ptgt = resolve(dim, p);
         c->top_ready = false;
         Cloud& cl = c->tgt;
@@ -2482,7 +2362,7 @@ int gicp_map_to_target(gicp_ctx* c, const gicp_params* p, int min_points) {
         cl.graph_ready = false;
         cl.dim = dim;
         cl.bits = dim == 3 ? 10 : 16;
-        build_core(cl, M, dim, mn, mx, c->ptgt, c->use_graph && c->use_certs, bs, st, false, 0, 1, kTile, tick, verbose, tlog);
+        build_core(cl, M, dim, mn, mx, c->ptgt, bs, target_spec(c, st), log);   // (the centroids are not filtered again)
         if (c->src.n) reset_tile_state(c);
     });
 }

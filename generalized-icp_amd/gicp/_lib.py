@@ -169,7 +169,7 @@ _lib = None
 
 # the sources gicp_build_info()'s hash covers, in the Makefile's HASH_SRCS order
 HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_voxel.hip",
-             "csrc/gicp_internal.h",
+             "csrc/gicp_internal.h", "csrc/gicp_mem.h",
              "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "../include/gicp_hip.h")
 
 

@@ -15,7 +15,10 @@
  *     buffers are library-owned.  No torch / HIP types cross this boundary.
  *   - Every int-returning call returns GICP_OK (0) or a negative GICP_E_*;
  *     gicp_last_error() then describes the failure.  No C++ exception
- *     crosses the boundary.
+ *     crosses the boundary.  After GICP_E_HIP / GICP_E_NOMEM from an
+ *     allocation the context stays usable and the failed call may be
+ *     repeated: a buffer that could not be allocated is left empty, never
+ *     half-built, and is allocated again then.
  *   - HIP is initialised lazily inside gicp_create(), never at load time, so
  *     the library is safe to load before fork() (robot-visualization.py:199
  *     runs gicp() in a forked worker).

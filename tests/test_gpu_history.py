@@ -13,10 +13,13 @@ A: d_c schedules on a warm context; B: the covariance model switched on a warm c
 (size, dimension, promotion, voxel filter, staged targets, the map, shards) on one context; D: every build
 path of a cloud (set_target, staged, staged with a borrowed buffer -- the last two run k_knn_cov with
 split = 1) at the edges of k_knn_cov; E: batch_hint and top_k_pref; F: a failed build leaves no half-built
-cloud.  make_engine, check_pass, VARIANTS and the covariance criteria are tests/gpu_helpers.py's, shared with
-test_gpu_edges.py."""
+cloud; G: engines taken from creation to close through every optional buffer group, four in turn, leave no
+device memory behind.  make_engine, check_pass, VARIANTS and the covariance criteria are tests/gpu_helpers.py's,
+shared with test_gpu_edges.py."""
 import ctypes as C
 import itertools
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -694,3 +697,147 @@ def test_failed_build_leaves_no_half_built_cloud(scenes, monkeypatch, call, kind
         check_step(e, monkeypatch, src, good, p, T, f"{call} {kind} {dim}-D after the rebuild")
     finally:
         e.close()
+
+
+# ============================================================================= G: a context's whole lifecycle
+BIG_M = 600_000                  # the larger target: 4 * BIG_M bytes is the bound on the memory growth below
+TOP_K = 5
+
+
+@pytest.fixture(scope="module")
+def big_target(scenes):
+    """BIG_M points of the room the 4000-point scenes are drawn from, in the target's frame."""
+    return S.scene_pair_3d(4000, BIG_M)[1]
+
+
+def lifecycle(e, monkeypatch, scenes, big, verify):
+    """One engine from creation to close through every optional buffer group: the voxel filter, both clouds,
+    the debug and top-k outputs, the trace rows, rotated covariances, a staged target committed and a borrowed
+    one cancelled, a promotion, the map, and a larger target so that the grow paths run.  Returns what each
+    step computed.  verify: every step is also held to the oracle and to a fresh engine that performs only
+    that step (check_step and the criteria of sections A and E)."""
+    s3, t3, T3 = scenes[3]
+    p = params(3)
+    I4 = np.eye(4)
+    moved = O.apply_transformation(s3, T3)
+    def step(src, tgt, p_, T, what, **kw):
+        return check_step(e, monkeypatch, src, tgt, p_, T, what, **kw) if verify else e.iterate(T, debug=True)
+    out = {}
+    try:
+        e.set_voxel(0.25)
+        e.set_target(t3, p)
+        e.set_source(s3, p)
+        out["voxel"] = step(s3, t3, p, T3, "G: voxel filter 0.25", voxel=0.25)
+        e.set_voxel(0)
+        e.set_target(t3, p)
+        e.set_source(s3, p)
+        out["pair"] = step(s3, t3, p, T3, "G: 4000 x 4000")
+        out["top"] = e.iterate_top(T3, TOP_K)
+        pa = params(3, max_iterations=2, fixed_iterations=1)
+        out["align"] = e.align(T3, pa, trace=True, top_k=TOP_K)
+        R = S.axis_angle([1.0, -2.0, 0.5], 0.3)
+        out["rot"] = e.rotated_covariances(R, "source")
+        if verify:
+            st, dbg = out["pair"]
+            det = np.linalg.det(dbg["weight"])
+            ref = np.argsort(det, kind="stable")[-TOP_K:]
+            _, si, ti, dt = out["top"]
+            assert np.array_equal(out["top"][0], st)
+            np.testing.assert_allclose(dt, det[ref], rtol=1e-9)
+            np.testing.assert_allclose(det[si], det[ref], rtol=1e-9)
+            assert np.array_equal(ti, dbg["index"][si])
+            _, res, tr = out["align"]
+            assert res["iterations"] == 2 and np.array_equal(tr["poses"][0], T3)
+            np.testing.assert_allclose(tr["top_det"][0], det[ref], rtol=1e-9)     # (the first pass ran at T3)
+            assert np.array_equal(tr["top_tgt"][0], dbg["index"][tr["top_src"][0]])
+            ref_rot = np.einsum("ab,nbc,dc->nad", R, e.covariances("source"), R)
+            np.testing.assert_allclose(out["rot"], ref_rot, rtol=0, atol=1e-12 * np.abs(ref_rot).max())
+            fresh = G.make_engine(monkeypatch)
+            try:
+                fresh.set_target(t3, p)
+                fresh.set_source(s3, p)
+                for x, y in zip(out["top"], fresh.iterate_top(T3, TOP_K)):
+                    assert np.array_equal(x, y), "G: iterate_top"
+                cold = fresh.align(T3, pa, trace=True, top_k=TOP_K)
+                same_align(out["align"], cold, "G: align")
+                for k in ("top_src", "top_tgt", "top_det"):
+                    assert np.array_equal(out["align"][2][k], cold[2][k]), ("G: align", k)
+                assert np.array_equal(out["rot"], fresh.rotated_covariances(R, "source")), "G: rotated covariances"
+            finally:
+                fresh.close()
+        e.stage_target(moved, p)                 # copied into the slot's pinned buffer
+        e.commit_target()                        # source <- t3, target <- moved
+        out["staged"] = step(t3, moved, p, I4, "G: staged target committed")
+        e.stage_target(np.ascontiguousarray(t3[:1500]), p, borrow=True)
+        e.cancel_stage()
+        e.target_to_source()                     # source <- moved, no target
+        e.map_reset(0.2, 1000.0, 3)
+        e.map_insert(I4, points=t3)
+        e.map_insert(I4, which="source")
+        cent = e.map_get()[1]
+        e.map_to_target(p)
+
+        def from_map(f):
+            f.set_source(moved, p)
+            f.map_reset(0.2, 1000.0, 3)
+            f.map_insert(I4, points=t3)
+            f.map_insert(I4, which="source")
+            f.map_to_target(p)
+        out["map"] = step(moved, cent, p, I4, "G: the map as target", build=from_map)
+        e.set_target(big, p)
+        out["big"] = step(moved, big, p, I4, "G: the larger target")
+    finally:
+        e.cancel_stage()
+        e.close()
+    return out
+
+
+# The device's free memory as torch reports it, read in a child process: hipMemGetInfo counts the whole device,
+# this process's allocations included, and torch brings its own HIP runtime, which finds no GPU when it is
+# initialised in a process where the library's runtime already holds one (which of the two comes first would
+# depend on the tests that ran before).  One child, started before the first cycle, answers every request.
+MEM_PROBE = """
+import sys, torch
+torch.cuda.init()
+print("ready", flush=True)
+for _ in sys.stdin:
+    torch.cuda.synchronize()
+    print(torch.cuda.mem_get_info(0)[0], flush=True)
+"""
+
+
+def test_lifecycle_leaves_no_memory_behind(scenes, big_target, monkeypatch):
+    """Four engines in turn, each created, taken through lifecycle() and closed (which synchronises its
+    streams).  The first one's steps are held to the oracle and to fresh engines; the other three must compute
+    the same bits.  The device's free memory (torch.cuda.mem_get_info after a synchronise, see MEM_PROBE) after
+    the fourth close may lie below its value after the first by less than one per-point int32 buffer of the
+    larger target, 4 * BIG_M bytes: a buffer that close() does not release would be lost three times over.
+    BIG_M is chosen so that this bound is above the 2 MiB steps in which the counter moves on an MI355X
+    (profiles/hostmem/README.md; measured growth there: 0 bytes, before and after the owners became DevBufs)."""
+    probe = subprocess.Popen([sys.executable, "-c", MEM_PROBE], stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+
+    def free_bytes():
+        probe.stdin.write("\n")
+        probe.stdin.flush()
+        line = probe.stdout.readline()
+        assert line.strip().isdigit(), f"the memory probe gave {line!r}"
+        return int(line)
+
+    try:
+        first = lifecycle(G.make_engine(monkeypatch), monkeypatch, scenes, big_target, verify=True)
+        assert probe.stdout.readline().strip() == "ready", "the memory probe could not initialise torch.cuda"
+        free1 = free_bytes()
+        for cycle in (2, 3, 4):
+            again = lifecycle(G.make_engine(monkeypatch), monkeypatch, scenes, big_target, verify=False)
+            for k in ("voxel", "pair", "staged", "map", "big"):
+                same_pass(first[k], again[k], f"G: cycle {cycle} {k}")
+            for x, y in zip(first["top"], again["top"]):
+                assert np.array_equal(x, y), cycle
+            same_align(first["align"], again["align"], f"G: cycle {cycle} align")
+            assert np.array_equal(first["rot"], again["rot"]), cycle
+        free4 = free_bytes()
+    finally:
+        probe.stdin.close()
+        probe.wait(timeout=60)
+    print(f"free after cycle 1: {free1}, after cycle 4: {free4}, growth {free1 - free4} bytes (bound {4 * BIG_M})")
+    assert free1 - free4 < 4 * BIG_M, (free1, free4)

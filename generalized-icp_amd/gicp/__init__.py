@@ -428,8 +428,9 @@ class Engine:
         return (st, out) if debug else st
 
     def pass_info(self):
-        """Diagnostics of the last pass: ambiguous lanes, pairs screened, list rebuilds, sum |r|^2,
-        lanes proved by the graph descent, source tiles that walked."""
+        """Diagnostics of the last pass: walking lanes the fp32 screen left ambiguous (re-resolved in fp64),
+        pairs screened, list rebuilds, sum |r|^2, lanes proved by the graph descent (its near ties, resolved
+        in fp64 from the row, included), source tiles that walked."""
         out = np.empty(_lib.PASS_INFO)
         check(self._lib.gicp_pass_info(self._ctx, dptr(out)), self._ctx, "gicp_pass_info")
         return dict(ambiguous=out[0], pairs=out[1], list_rebuilds=out[2], sum_sq=out[3], graph_proved=out[4],

@@ -270,9 +270,11 @@ int gicp_get_neighbor_counts(gicp_ctx* ctx, int which, int32_t* out);
 int gicp_iterate(gicp_ctx* ctx, const double* T, double* stats, gicp_debug* dbg);
 
 /* Per-pass diagnostics of the last gicp_iterate / gicp_align pass, summed over ranks:
- * out[0] ambiguous lanes re-resolved in fp64, out[1] distance pairs screened, out[2] candidate-list
- * rebuilds, out[3] sum of squared correspondence distances |q - (R s + t)|^2 (PCL's MSE numerator),
- * out[4] points whose nearest target the graph descent proved, out[5] source tiles that walked. */
+ * out[0] walking lanes whose fp32 screen was ambiguous, re-resolved in fp64 (a near tie that the graph
+ * descent resolves in fp64 from its row counts in out[4], not here), out[1] distance pairs screened,
+ * out[2] candidate-list rebuilds, out[3] sum of squared correspondence distances |q - (R s + t)|^2 (PCL's
+ * MSE numerator), out[4] points whose nearest target the graph descent proved, out[5] source tiles that
+ * walked. */
 #define GICP_PASS_INFO 6
 int gicp_pass_info(gicp_ctx* ctx, double out[GICP_PASS_INFO]);
 

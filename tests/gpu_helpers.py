@@ -17,8 +17,18 @@ DEFAULTS = dict(GICP_NO_CERTS="0", GICP_NO_LISTS="0", GICP_NO_GRAPH="0", GICP_SP
                 GICP_SRC_TILE="64")
 
 
+LIBRARY = "LIBRARY_DEFAULTS"   # make_engine(**{LIBRARY: "1"}): none of the GICP_* switches set
+
+
 def make_engine(monkeypatch, **env):
-    """An engine created under the given GICP_* switches (read at creation), the others at their defaults."""
+    """An engine created under the given GICP_* switches (read at creation), the others at DEFAULTS; with
+    LIBRARY given, with every switch unset, so that the library's own defaults are what runs (they are not
+    DEFAULTS: the library walks sparsely up to 4 lanes, DEFAULTS pins GICP_SPARSE_WALK=2)."""
+    if env.pop(LIBRARY, None):
+        assert not env, env
+        for k in FLAGS:
+            monkeypatch.delenv(k, raising=False)
+        return gicp.Engine(0)
     for k in FLAGS:
         monkeypatch.setenv(k, str(env.get(k, DEFAULTS[k])))
     e = gicp.Engine(0)
@@ -30,7 +40,8 @@ def make_engine(monkeypatch, **env):
 VARIANTS = {"default": {}, "no_certs": dict(GICP_NO_CERTS="1"), "no_lists": dict(GICP_NO_LISTS="1"),
             "plain": dict(GICP_NO_CERTS="1", GICP_NO_LISTS="1"), "no_graph": dict(GICP_NO_GRAPH="1"),
             "sparse_walk_0": dict(GICP_SPARSE_WALK="0"), "sparse_walk_64": dict(GICP_SPARSE_WALK="64"),
-            "sparse_amb_0": dict(GICP_SPARSE_AMB="0"), "sparse_amb_64": dict(GICP_SPARSE_AMB="64")}
+            "sparse_amb_0": dict(GICP_SPARSE_AMB="0"), "sparse_amb_64": dict(GICP_SPARSE_AMB="64"),
+            "library": {LIBRARY: "1"}}
 
 
 def check_pass(eng, src, tgt, T, d_c, model="plane_to_plane", min_neighbors=None, what="", coord_atol=False):

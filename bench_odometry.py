@@ -3,6 +3,7 @@
 
     python bench_odometry.py [--frames 1000] [--max-iterations 30] [--fixed]
     python bench_odometry.py --map-voxel 0.4 --map-range 30     # the same stream, scan-to-map
+    python bench_odometry.py --skew [--deskew]                  # sweeps measured while the sensor moves (§3m)
 
 Prints one JSON line: GICP iterations/sec over the registration loops, frames/sec end to end
 (upload + index + covariances + registration per frame), setup per frame, and the trajectory
@@ -41,7 +42,14 @@ def main():
                          "and merged into it (needs --map-range; default: scan-to-scan)")
     ap.add_argument("--map-range", type=float, default=None, help="reach of the local map from the sensor (metres)")
     ap.add_argument("--map-min-points", type=int, default=1, help="voxels with fewer points are not registered against")
+    ap.add_argument("--skew", action="store_true",
+                    help="every ray is cast from the pose the sensor has at its stamp (synthetic.lidar_stream_skewed, "
+                         "generated with NumPy); poses are compared at mid-sweep")
+    ap.add_argument("--deskew", action="store_true",
+                    help="de-skew every scan on the device as part of its build (Odometry(deskew=True); needs --skew)")
     a = ap.parse_args()
+    if a.deskew and not a.skew:
+        ap.error("--deskew needs --skew (the plain stream carries no stamps)")
     if (a.map_voxel is None) != (a.map_range is None):
         ap.error("--map-voxel and --map-range go together")
     from gicp import synthetic as S
@@ -54,7 +62,12 @@ def main():
     except ImportError:
         pass
     t0 = time.perf_counter()
-    frames = list(S.lidar_stream(a.frames, a.beams, a.azimuths, xp=xp, device=dev))
+    if a.skew:
+        frames = list(S.lidar_stream_skewed(a.frames, a.beams, a.azimuths))
+        if not a.deskew:   # the skewed points as they are: the stamps are dropped
+            frames = [(np.ascontiguousarray(f[:, :3]), P) for f, P in frames]
+    else:
+        frames = list(S.lidar_stream(a.frames, a.beams, a.azimuths, xp=xp, device=dev))
     gen_s = time.perf_counter() - t0
     kw = dict(max_distance_correspondence=0.5, max_distance_nearest_neighbors=1.0)
     import gicp
@@ -65,7 +78,7 @@ def main():
         # two launches); --kernel-times keeps the library default (every 8th launch timed)
         p.timing_stride = -1
     odo = Odometry(3, params=p, borrow=not a.copy, voxel_size=a.voxel_size, map_voxel_size=a.map_voxel,
-                   map_range=a.map_range, map_min_points=a.map_min_points)
+                   map_range=a.map_range, map_min_points=a.map_min_points, deskew=a.deskew)
     # warm-up on the first two frames (library init, allocation), then restart the stream
     odo.step(frames[0][0])
     odo.step(frames[1][0], frames[2][0])
@@ -120,6 +133,14 @@ def main():
                   "path_length": float(sum(np.linalg.norm(frames[k][1][:3, 3] - frames[k - 1][1][:3, 3])
                                            for k in range(1, len(frames))))},
     }
+    if a.skew:
+        est = [P0 @ P for P in odo.poses]
+        pos_err = [float(np.linalg.norm(E[:3, 3] - f[1][:3, 3])) for E, f in zip(est, frames)]
+        line["data"] = f"synthetic spinning LiDAR, {a.beams}x{a.azimuths} rays, C2 room, every ray cast from the pose at " \
+                       f"its stamp (generated in {gen_s:.1f} s, numpy)"
+        line["skew"] = {"deskew": bool(a.deskew), "pose_reference_stamp": 0.5,
+                        "pose_error_final": pos_err[-1], "pose_error_median": float(np.median(pos_err[1:])),
+                        "pose_error_max": float(np.max(pos_err))}
     if a.voxel_size is not None:
         line["voxel"] = {"voxel_size": a.voxel_size, "points_last_frame": odo.eng.cloud_size("source" if a.map_voxel else "target")}
     if a.map_voxel is not None:

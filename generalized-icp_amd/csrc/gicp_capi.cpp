@@ -29,6 +29,7 @@
 #include "../../include/gicp_hip.h"
 #include "gicp_internal.h"
 #include "gicp_mem.h"
+#include "gicp_sweep.h"
 
 namespace gicp {
 hipError_t launch_morton(const double*, int64_t, int, const DevCloud&, uint32_t*, int32_t*, hipStream_t);
@@ -47,6 +48,7 @@ hipError_t launch_top_weights(const double*, const int64_t*, const int32_t*, int
 hipError_t voxel_temp_bytes(int64_t, int, size_t*, hipStream_t);
 hipError_t launch_voxel(const VoxelArgs&, hipStream_t);
 hipError_t launch_points_out(const double*, const int32_t*, int64_t, int, double*, hipStream_t);
+hipError_t launch_deskew(const SweepArgs&, hipStream_t);
 hipError_t launch_map_insert(const VoxelArgs&, const MapArgs&, hipStream_t);
 hipError_t launch_map_centroids(const double*, int64_t, int, int, int32_t*, int32_t*, void*, size_t, double*,
                                 unsigned long long*, hipStream_t);
@@ -248,6 +250,7 @@ struct BuildScratch {
     DevBuf<int2> v_cmeta;
     DevBuf<unsigned char> v_tmp;
     DevBuf<unsigned long long> v_res;
+    DevBuf<double> w_stamps;          // the stamps of a sweep (gicp_sweep.hip)
     std::unique_ptr<WorkerPool> pool;  // tiling threads (lazily started)
     WorkerPool& workers() {
         if (!pool) {
@@ -286,6 +289,14 @@ struct BuildSpec {
     // voxel filter, on the device), and the index is built over those centroids in key order
     double voxel_leaf = 0.0;
     int voxel_min = 1;
+    // sweep: the uploaded cloud is first de-skewed on the device, point i moved by
+    // Exp((stamps[i] - ref) Log(motion)); the filter and the index then see the de-skewed points and their bounds.
+    // The twist is taken from `motion` ((dim+1)^2 row-major) once the build has begun, so a motion it refuses
+    // leaves the cloud NOT SET
+    bool sweep = false;
+    const double* stamps = nullptr;   // [n] host, read during the build
+    double motion[16] = {};
+    double ref = 0.0;
     hipStream_t stream = nullptr;
 };
 
@@ -757,6 +768,122 @@ VoxelOut voxel_filter(BuildScratch& bs, const double* d_raw, int64_t n, int dim,
     return vo;
 }
 
+// ---- motion compensation (gicp_sweep.h) ----
+
+// The twist xi = Log(M) of a rigid motion M ((dim+1)^2 row-major, last row not read): 3-D (omega[3], v[3]),
+// 2-D (omega, v[2]).  Refuses what is no constant-velocity sweep: a non-finite M, a linear part that is no
+// rotation, more than a quarter turn per stamp unit (which also keeps Log well conditioned: theta <= pi / 2).
+void motion_twist(int dim, const double* M, double* xi) {
+    if (dim != 2 && dim != 3) throw Fail{GICP_E_INVALID, "dim must be 2 or 3"};
+    if (!M || !xi) throw Fail{GICP_E_INVALID, "motion and twist must not be NULL"};
+    const int w = dim + 1;
+    double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
+    for (int r = 0; r < dim; ++r) {
+        for (int c = 0; c < w; ++c)
+            if (!std::isfinite(M[r * w + c])) throw Fail{GICP_E_INVALID, "motion contains non-finite values"};
+        for (int c = 0; c < dim; ++c) R[r][c] = M[r * w + c];
+        t[r] = M[r * w + dim];
+    }
+    double dev = 0.0;
+    for (int a = 0; a < dim; ++a)
+        for (int b = 0; b < dim; ++b) {
+            double g = a == b ? -1.0 : 0.0;
+            for (int k = 0; k < dim; ++k) g += R[k][a] * R[k][b];
+            dev = std::max(dev, std::fabs(g));
+        }
+    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+    if (!(dev <= 1e-9) || !(det > 0.0)) {
+        char b[128];
+        std::snprintf(b, sizeof b, "motion is not rigid: max|R^T R - I| = %.3g (at most 1e-9), det R = %.3g", dev, det);
+        throw Fail{GICP_E_INVALID, b};
+    }
+    const char* turn = "motion rotates by more than a quarter turn per stamp unit";
+    double A, B, C;
+    if (dim == 3) {
+        const double cs = 0.5 * (R[0][0] + R[1][1] + R[2][2] - 1.0);
+        if (cs < 0.0) throw Fail{GICP_E_INVALID, turn};
+        // a = sin(theta) axis, from the skew part; theta = atan2(|a|, cos(theta)) is accurate at every angle
+        const double a[3] = {0.5 * (R[2][1] - R[1][2]), 0.5 * (R[0][2] - R[2][0]), 0.5 * (R[1][0] - R[0][1])};
+        const double sn = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        const double f = sn > 0.0 ? std::atan2(sn, cs) / sn : 1.0;
+        const double o[3] = {f * a[0], f * a[1], f * a[2]};
+        sweep_coeffs(o[0] * o[0] + o[1] * o[1] + o[2] * o[2], A, B, C);
+        // v solves V v = t, V = I + B o^ + C o^2 (o^2 = o o^T - |o|^2 I)
+        const double K[3][3] = {{0, -o[2], o[1]}, {o[2], 0, -o[0]}, {-o[1], o[0], 0}};
+        double V[3][3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                double k2 = 0.0;
+                for (int k = 0; k < 3; ++k) k2 += K[r][k] * K[k][c];
+                V[r][c] = (r == c ? 1.0 : 0.0) + B * K[r][c] + C * k2;
+            }
+        const double c00 = V[1][1] * V[2][2] - V[1][2] * V[2][1], c01 = V[1][2] * V[2][0] - V[1][0] * V[2][2],
+                     c02 = V[1][0] * V[2][1] - V[1][1] * V[2][0];
+        const double dV = V[0][0] * c00 + V[0][1] * c01 + V[0][2] * c02;
+        const double inv[3][3] = {
+            {c00, V[0][2] * V[2][1] - V[0][1] * V[2][2], V[0][1] * V[1][2] - V[0][2] * V[1][1]},
+            {c01, V[0][0] * V[2][2] - V[0][2] * V[2][0], V[0][2] * V[1][0] - V[0][0] * V[1][2]},
+            {c02, V[0][1] * V[2][0] - V[0][0] * V[2][1], V[0][0] * V[1][1] - V[0][1] * V[1][0]}};
+        for (int r = 0; r < 3; ++r) {
+            xi[r] = o[r];
+            xi[3 + r] = (inv[r][0] * t[0] + inv[r][1] * t[1] + inv[r][2] * t[2]) / dV;
+        }
+    } else {
+        if (R[0][0] < 0.0) throw Fail{GICP_E_INVALID, turn};
+        const double o = std::atan2(R[1][0] - R[0][1], R[0][0] + R[1][1]);
+        sweep_coeffs(o * o, A, B, C);
+        // V = (A  -B o; B o  A)
+        const double Bo = B * o, dV = A * A + Bo * Bo;
+        xi[0] = o;
+        xi[1] = (A * t[0] + Bo * t[1]) / dV;
+        xi[2] = (A * t[1] - Bo * t[0]) / dV;
+    }
+}
+
+// the finiteness test of a sweep's stamps and reference stamp (v - v is NaN for NaN and +-inf)
+void scan_stamps(const double* stamps, int64_t n, double ref) {
+    if (!std::isfinite(ref)) throw Fail{GICP_E_INVALID, "sweep reference stamp is not finite"};
+    double acc = 0.0;
+    for (int64_t i = 0; i < n; ++i) acc += stamps[i] - stamps[i];
+    if (!(acc == 0.0)) throw Fail{GICP_E_INVALID, "sweep contains non-finite stamps"};
+}
+
+template <int D>
+void deskew_host(const double* xyz, const double* stamps, int64_t n, const double* xi, double ref, double* out) {
+    for (int64_t i = 0; i < n; ++i) sweep_point<D>(xi, stamps[i] - ref, xyz + i * D, out + i * D);
+}
+
+// De-skew the device cloud d_pts [n][dim] in place on `st` (gicp_sweep.hip): the host stamps are uploaded into
+// bs.w_stamps, the ordered-integer bounds of the result land in bs.v_res[0..5] (deskew_decode decodes them).
+void deskew_launch(BuildScratch& bs, double* d_pts, const double* stamps, int64_t n, int dim, const double* xi, double ref,
+                   hipStream_t st) {
+    bs.w_stamps.reserve((size_t)n);
+    if (!bs.v_res) bs.v_res.alloc((size_t)kVoxelRes);
+    HIPCHK(hipMemcpyAsync(bs.w_stamps, stamps, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    SweepArgs sa{};
+    sa.pts = d_pts;
+    sa.stamps = bs.w_stamps;
+    sa.n = n;
+    sa.dim = dim;
+    for (int k = 0; k < (dim == 3 ? 6 : 3); ++k) sa.xi[k] = xi[k];
+    sa.ref = ref;
+    sa.res = bs.v_res;
+    HIPCHK(launch_deskew(sa, st));
+}
+
+// the exact bounds of the de-skewed points, decoded from the result words (synchronised by the caller)
+void deskew_decode(const unsigned long long* res, int dim, double (&mn)[3], double (&mx)[3]) {
+    for (int a = 0; a < 3; ++a) mn[a] = mx[a] = 0.0;
+    for (int a = 0; a < dim; ++a) {
+        mn[a] = dec_ordered(res[a]);
+        mx[a] = dec_ordered(res[3 + a]);
+        // (finite stamps times a finite twist can still overflow; a NaN coordinate decodes as a NaN bound)
+        if (!std::isfinite(mn[a]) || !std::isfinite(mx[a]))
+            throw Fail{GICP_E_INVALID, "de-skewed cloud is not finite (stamps too large for the motion)"};
+    }
+}
+
 void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
                 BuildScratch& bs, const BuildSpec& spec, BuildLog& log);
 
@@ -766,6 +893,7 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
                  const BuildSpec& spec) {
     if (!xyz || n <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
     if (n > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cloud too large (> 2^31 points)"};
+    if (spec.sweep && !spec.stamps) throw Fail{GICP_E_INVALID, "a sweep needs stamps (gicp_sweep.stamps is NULL)"};
     hipStream_t st = spec.stream;
     BuildLog log(st);
     cl.n = 0;   // buffers are kept (grow-only) and reused
@@ -775,18 +903,35 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
     cl.bits = dim == 3 ? 10 : 16;
     double mn[3], mx[3];
     scan_bounds(xyz, n, dim, mn, mx);
+    double xi[6];
+    if (spec.sweep) {
+        scan_stamps(spec.stamps, n, spec.ref);
+        motion_twist(dim, spec.motion, xi);
+    }
     log.tick("host-scan");
     bs.s_in.reserve((size_t)n * dim);
+    // A sweep is de-skewed in place where it was uploaded; the filter and the index then take the device's
+    // exact bounds of the de-skewed points (one stream sync) in place of the host scan's.
+    auto deskew = [&](double* d_pts) {
+        deskew_launch(bs, d_pts, spec.stamps, n, dim, xi, spec.ref, st);
+        unsigned long long res[kVoxelRes];
+        HIPCHK(hipMemcpyAsync(res, bs.v_res, sizeof res, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        deskew_decode(res, dim, mn, mx);
+        log.tick("deskew");
+    };
     // (a staged build passes its pinned copy: the H2D copy is then asynchronous)
     if (spec.voxel_leaf > 0.0) {
         bs.v_raw.reserve((size_t)n * dim);
         HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
+        if (spec.sweep) deskew(bs.v_raw);
         const VoxelOut vo = voxel_filter(bs, bs.v_raw, n, dim, mn, mx, spec.voxel_leaf, spec.voxel_min, bs.s_in, st);
         n = vo.M;
         for (int a = 0; a < 3; ++a) mn[a] = vo.mn[a], mx[a] = vo.mx[a];
         log.tick("voxel");
     } else {
         HIPCHK(hipMemcpyAsync(bs.s_in, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
+        if (spec.sweep) deskew(bs.s_in);
     }
     build_core(cl, n, dim, mn, mx, p, bs, spec, log);
 }
@@ -1018,6 +1163,15 @@ BuildSpec target_spec(const gicp_ctx* c, hipStream_t st) {
     spec.voxel_min = c->voxel_min;
     spec.stream = st;
     return spec;
+}
+
+// the optional sweep of a build (NULL: a plain cloud)
+void take_sweep(BuildSpec& spec, const gicp_sweep* sw, int dim) {
+    if (!sw) return;
+    spec.sweep = true;
+    spec.stamps = sw->stamps;
+    spec.ref = sw->ref;
+    if (dim == 2 || dim == 3) std::memcpy(spec.motion, sw->motion, sizeof(double) * (dim + 1) * (dim + 1));
 }
 
 VoxelMap& need_map(gicp_ctx* c) {
@@ -1349,7 +1503,7 @@ int guard_impl(gicp_ctx* c, const char* where, const std::function<void()>& body
 
 extern "C" {
 
-int gicp_version(void) { return 101; }
+int gicp_version(void) { return 102; }
 
 int gicp_stats_size(int dim) { return (dim == 2 || dim == 3) ? nstat(dim == 2 ? 2 : 3) : GICP_E_INVALID; }
 
@@ -1489,17 +1643,28 @@ int gicp_comm_ranks(gicp_ctx* c, int* nranks, int* rank, int* kind) {
 }
 
 int gicp_set_target(gicp_ctx* c, const double* xyz, int64_t M, int dim, const gicp_params* p) {
+    return gicp_set_target_sweep(c, xyz, M, dim, p, nullptr);
+}
+
+int gicp_set_target_sweep(gicp_ctx* c, const double* xyz, int64_t M, int dim, const gicp_params* p, const gicp_sweep* sw) {
     if (!c) return GICP_E_INVALID;
     return guard_impl(c, "gicp_set_target", [&] {
         c->ptgt = resolve(dim, p);
         c->top_ready = false;
-        build_cloud(c->tgt, xyz, M, dim, c->ptgt, c->bs, target_spec(c, c->stream));
+        BuildSpec spec = target_spec(c, c->stream);
+        take_sweep(spec, sw, dim);
+        build_cloud(c->tgt, xyz, M, dim, c->ptgt, c->bs, spec);
         if (c->src.n) reset_tile_state(c);
     });
 }
 
 int gicp_set_source(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gicp_params* p, int shard,
                     int nshards) {
+    return gicp_set_source_sweep(c, xyz, N, dim, p, shard, nshards, nullptr);
+}
+
+int gicp_set_source_sweep(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gicp_params* p, int shard,
+                          int nshards, const gicp_sweep* sw) {
     if (!c) return GICP_E_INVALID;
     return guard_impl(c, "gicp_set_source", [&] {
         if (nshards < 1 || shard < 0 || shard >= nshards) throw Fail{GICP_E_INVALID, "bad shard / nshards"};
@@ -1512,6 +1677,7 @@ int gicp_set_source(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gi
         spec.voxel_leaf = c->voxel_leaf;
         spec.voxel_min = c->voxel_min;
         spec.stream = c->stream;
+        take_sweep(spec, sw, dim);
         build_cloud(c->src, xyz, N, dim, c->psrc, c->bs, spec);
         set_shard(c, shard, nshards);
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1916,26 +2082,38 @@ int gicp_stage_target(gicp_ctx* c, const double* xyz, int64_t M, int dim, const 
 }
 
 int gicp_stage_target_ex(gicp_ctx* c, const double* xyz, int64_t M, int dim, const gicp_params* p, int flags) {
+    return gicp_stage_target_sweep(c, xyz, M, dim, p, flags, nullptr);
+}
+
+int gicp_stage_target_sweep(gicp_ctx* c, const double* xyz, int64_t M, int dim, const gicp_params* p, int flags,
+                            const gicp_sweep* sw) {
     if (!c) return GICP_E_INVALID;
     return guard_impl(c, "gicp_stage_target", [&] {
         if (c->stg_count >= GICP_MAX_STAGED)
             throw Fail{GICP_E_STATE, "GICP_MAX_STAGED staged targets are pending (gicp_commit_target or gicp_cancel_stage first)"};
         if (!xyz || M <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
         if (flags & ~GICP_STAGE_BORROW) throw Fail{GICP_E_INVALID, "unknown gicp_stage_target_ex flags"};
+        if (sw) {   // a sweep no build would take is refused here, with no slot used
+            if (!sw->stamps) throw Fail{GICP_E_INVALID, "a sweep needs stamps (gicp_sweep.stamps is NULL)"};
+            double xi[6];
+            motion_twist(dim, sw->motion, xi);
+        }
         gicp_ctx::Staged& g = c->stg[(c->stg_head + c->stg_count) % GICP_MAX_STAGED];
         g.wait_idle();   // (a slot is only reused after its commit or cancel; a build never runs here)
         const gicp_params prm = resolve(dim, p);
         if (!g.stream) HIPCHK(hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking));
         const double* src = xyz;
+        const double* stamps = sw ? sw->stamps : nullptr;
         if (!(flags & GICP_STAGE_BORROW)) {
-            const size_t need = (size_t)M * dim;
+            // (the stamps of a sweep lie behind the points in the same pinned buffer)
+            const size_t need = (size_t)M * dim + (sw ? (size_t)M : 0);
             // grow-only pinned staging buffer (allocated here, not in the worker), with headroom from the first
             // allocation on: need / 8
             if (need > g.bs.h_pinned.capacity()) g.bs.h_pinned.alloc(need + need / 8);
             // the caller's scan is copied into the slot's pinned buffer before this call returns (the caller
             // may refill its buffer at once): 16 fixed chunks on the calling thread's tiling pool (a 100k-point
             // frame, 2.4 MB, in ~0.06 ms instead of one thread's ~0.3 ms)
-            const size_t total = sizeof(double) * need;
+            const size_t total = sizeof(double) * (size_t)M * dim;
             char* dst = reinterpret_cast<char*>(g.bs.h_pinned.get());
             const char* srcb = reinterpret_cast<const char*>(xyz);
             constexpr int kChunks = 16;
@@ -1944,6 +2122,11 @@ int gicp_stage_target_ex(gicp_ctx* c, const double* xyz, int64_t M, int dim, con
                 std::memcpy(dst + b0, srcb + b0, b1 - b0);
             });
             src = g.bs.h_pinned;
+            if (sw) {
+                double* ds = g.bs.h_pinned.get() + (size_t)M * dim;
+                std::memcpy(ds, sw->stamps, sizeof(double) * (size_t)M);
+                stamps = ds;
+            }
         }
         if (!g.th.joinable()) g.th = std::thread(staged_worker, &g);
         {
@@ -1954,6 +2137,8 @@ int gicp_stage_target_ex(gicp_ctx* c, const double* xyz, int64_t M, int dim, con
             g.device = c->device;
             g.spec = target_spec(c, g.stream);
             g.spec.staged = true;
+            take_sweep(g.spec, sw, dim);
+            g.spec.stamps = stamps;
             g.p = prm;
             g.rc = GICP_OK;
             g.err.clear();
@@ -2228,6 +2413,68 @@ int gicp_get_points(gicp_ctx* c, int which, double* out) {
         HIPCHK(launch_points_out(cl.xyz64, cl.perm, cl.n, cl.dim, c->d_rot, c->stream));
         HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+// ---- motion compensation ----
+
+namespace {
+// a host-only entry point's body: no context, no HIP call
+int host_guard(const std::function<void()>& body) {
+    try {
+        body();
+        return GICP_OK;
+    } catch (const Fail& f) {
+        return f.code;
+    } catch (...) {
+        return GICP_E_INVALID;
+    }
+}
+
+void check_sweep_args(const double* xyz, const double* stamps, int64_t N, int dim, const double* out) {
+    if (!xyz || N <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
+    if (N > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cloud too large (> 2^31 points)"};
+    if (!stamps) throw Fail{GICP_E_INVALID, "a sweep needs stamps (stamps is NULL)"};
+    if (!out) throw Fail{GICP_E_INVALID, "out must not be NULL"};
+}
+}  // namespace
+
+int gicp_motion_twist(int dim, const double* M, double* xi) {
+    return host_guard([&] { motion_twist(dim, M, xi); });
+}
+
+int gicp_deskew_host(const double* xyz, const double* stamps, int64_t N, int dim, const double* M, double ref,
+                     double* out) {
+    return host_guard([&] {
+        check_sweep_args(xyz, stamps, N, dim, out);
+        double mn[3], mx[3], xi[6];
+        scan_bounds(xyz, N, dim, mn, mx);   // (the finiteness test)
+        scan_stamps(stamps, N, ref);
+        motion_twist(dim, M, xi);
+        if (dim == 3) deskew_host<3>(xyz, stamps, N, xi, ref, out);
+        else deskew_host<2>(xyz, stamps, N, xi, ref, out);
+    });
+}
+
+int gicp_deskew(gicp_ctx* c, const double* xyz, const double* stamps, int64_t N, int dim, const double* M, double ref,
+                double* out) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_deskew", [&] {
+        check_sweep_args(xyz, stamps, N, dim, out);
+        double mn[3], mx[3], xi[6];
+        scan_bounds(xyz, N, dim, mn, mx);   // (the finiteness test)
+        scan_stamps(stamps, N, ref);
+        motion_twist(dim, M, xi);
+        BuildScratch& bs = c->bs;
+        hipStream_t st = c->stream;
+        bs.s_in.reserve((size_t)N * dim);
+        HIPCHK(hipMemcpyAsync(bs.s_in, xyz, sizeof(double) * N * dim, hipMemcpyHostToDevice, st));
+        deskew_launch(bs, bs.s_in, stamps, N, dim, xi, ref, st);
+        unsigned long long res[kVoxelRes];
+        HIPCHK(hipMemcpyAsync(out, bs.s_in, sizeof(double) * N * dim, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(res, bs.v_res, sizeof res, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        deskew_decode(res, dim, mn, mx);   // (refuses a result that is not finite)
     });
 }
 

@@ -22,7 +22,7 @@ from . import _lib
 from ._lib import Debug, Params, Result, Trace, check, dptr
 
 __all__ = ["gicp", "apply_transformation", "Engine", "RotatedCovariances", "expand_stats", "stats_size",
-           "default_params", "last_result", "voxel_downsample"]
+           "default_params", "last_result", "voxel_downsample", "deskew", "deskew_host", "motion_twist"]
 
 
 def stats_size(dim):
@@ -184,20 +184,52 @@ class Engine:
         check(_lib.load().gicp_comm_unique_id(buf), None, "gicp_comm_unique_id")
         return buf.raw
 
-    def set_target(self, pts, params=None):
+    @staticmethod
+    def _sweep(a, stamps, motion, ref):
+        """(gicp_sweep, the stamps array it points into) of the cloud `a`."""
+        d = a.shape[1]
+        st = np.ascontiguousarray(np.asarray(stamps, dtype=np.float64))
+        if st.shape != (a.shape[0],):
+            raise ValueError(f"stamps must hold one value per point ({a.shape[0]}), got shape {st.shape}")
+        if motion is None:
+            raise ValueError("a sweep needs its motion (stamps given, motion None)")
+        M = np.asarray(motion, dtype=np.float64)
+        if M.shape != (d + 1, d + 1):
+            raise ValueError(f"motion must be {d + 1} x {d + 1}, got shape {M.shape}")
+        sw = _lib.Sweep()
+        sw.stamps = dptr(st)
+        sw.ref = float(ref)
+        for k, v in enumerate(M.ravel()):
+            sw.motion[k] = v
+        return sw, st
+
+    def set_target(self, pts, params=None, stamps=None, motion=None, ref=0.0):
+        """Index `pts` as the target.  With `stamps` (one per point) the cloud is a sweep: it is de-skewed on
+        the device by the rigid `motion` per stamp unit to the reference stamp `ref` before it is filtered and
+        indexed (gicp_set_target_sweep; see `deskew`)."""
         a = self._cloud(pts)
         p = params or default_params(a.shape[1])
-        check(self._lib.gicp_set_target(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p)), self._ctx,
-              "gicp_set_target")
+        if stamps is None:
+            rc = self._lib.gicp_set_target(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p))
+        else:
+            sw, _keep = self._sweep(a, stamps, motion, ref)
+            rc = self._lib.gicp_set_target_sweep(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), C.byref(sw))
+        check(rc, self._ctx, "gicp_set_target")
         self.n_tgt, self.dim = a.shape
         if self.voxel[0] > 0:
             self.n_tgt = self.cloud_size("target")
 
-    def set_source(self, pts, params=None, shard=0, nshards=1):
+    def set_source(self, pts, params=None, shard=0, nshards=1, stamps=None, motion=None, ref=0.0):
+        """Index `pts` as the source; `stamps`, `motion`, `ref` as in set_target (gicp_set_source_sweep)."""
         a = self._cloud(pts)
         p = params or default_params(a.shape[1])
-        check(self._lib.gicp_set_source(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), shard, nshards),
-              self._ctx, "gicp_set_source")
+        if stamps is None:
+            rc = self._lib.gicp_set_source(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), shard, nshards)
+        else:
+            sw, _keep = self._sweep(a, stamps, motion, ref)
+            rc = self._lib.gicp_set_source_sweep(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), shard, nshards,
+                                                 C.byref(sw))
+        check(rc, self._ctx, "gicp_set_source")
         self.n_src, self.dim = a.shape
         if self.voxel[0] > 0:
             self.n_src = self.cloud_size("source")
@@ -211,18 +243,26 @@ class Engine:
 
     MAX_STAGED = 2   # GICP_MAX_STAGED
 
-    def stage_target(self, pts, params=None, borrow=False):
+    def stage_target(self, pts, params=None, borrow=False, stamps=None, motion=None, ref=0.0):
         """Build `pts` as a coming target on its own stream while the current one is registered
         (gicp_stage_target; up to MAX_STAGED pending); commit_target makes the oldest current.  The
         library copies `pts` before this call returns, so the caller may reuse the array at once --
         unless borrow=True (GICP_STAGE_BORROW): then the build reads the array itself (no copy on this
         thread) and the caller must not modify it until commit_target / cancel_stage (this object keeps
-        a reference until then)."""
+        a reference until then).  `stamps`, `motion`, `ref` as in set_target (gicp_stage_target_sweep); the
+        stamps are copied or borrowed with the points."""
         a = self._cloud(pts)
         p = params or default_params(a.shape[1])
-        check(self._lib.gicp_stage_target_ex(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p),
-                                             _lib.GICP_STAGE_BORROW if borrow else 0), self._ctx, "gicp_stage_target")
-        self._staged.append((a.shape, p, a if borrow else None, self.voxel[0] > 0))
+        flags = _lib.GICP_STAGE_BORROW if borrow else 0
+        st = None
+        if stamps is None:
+            rc = self._lib.gicp_stage_target_ex(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), flags)
+        else:
+            sw, st = self._sweep(a, stamps, motion, ref)
+            rc = self._lib.gicp_stage_target_sweep(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), flags,
+                                                   C.byref(sw))
+        check(rc, self._ctx, "gicp_stage_target")
+        self._staged.append((a.shape, p, (a, st) if borrow else None, self.voxel[0] > 0))
 
     def commit_target(self, shard=0, nshards=1):
         """Wait for the oldest staged target; the current target becomes the source, the staged one the target."""
@@ -264,6 +304,16 @@ class Engine:
                                               C.byref(m)), self._ctx, "gicp_voxel_downsample")
         out = out[:m.value].copy()
         return (out, cnt[:m.value].copy()) if return_counts else out
+
+    def deskew(self, points, stamps, motion, ref=0.0):
+        """gicp.deskew on this engine's GPU (gicp_deskew); the engine's clouds are untouched."""
+        a = self._cloud(points)
+        _, st = self._sweep(a, stamps, motion, ref)   # (the shape checks)
+        M = np.ascontiguousarray(np.asarray(motion, dtype=np.float64))
+        out = np.empty_like(a)
+        check(self._lib.gicp_deskew(self._ctx, dptr(a), dptr(st), a.shape[0], a.shape[1], dptr(M), float(ref),
+                                    dptr(out)), self._ctx, "gicp_deskew")
+        return out
 
     def cloud_size(self, which="target"):
         """Points the indexed cloud holds (gicp_cloud_size): the input's length, or with a voxel filter
@@ -629,6 +679,41 @@ def voxel_downsample(points, voxel_size, min_points=1, return_counts=False, devi
     not finite and positive, non-finite points, a cloud spanning more than 2^21 (3-D) / 2^31 (2-D) cells
     along an axis, and when no cell reaches min_points."""
     return _engine(int(device)).voxel_downsample(points, voxel_size, min_points, return_counts)
+
+
+def deskew(points, stamps, motion, ref=0.0, device=0):
+    """Motion compensation of a sweep on the GPU (gicp_deskew): `points` (N x 2 or N x 3) were
+    measured one by one while the sensor moved, point i at stamp `stamps[i]`; `motion` is the rigid
+    (dim+1) x (dim+1) transform of the sensor over one stamp unit, expressed in the sensor frame,
+    P(tau)^-1 P(tau + 1).  Returns the points as seen from the sensor frame at stamp `ref` under constant twist:
+    p'_i = Exp((stamps[i] - ref) Log(motion)) p_i, in fp64, rows in their order.  Deterministic: the same bits
+    on every call and GPU, and the rows Engine.set_target(..., stamps=, motion=, ref=) indexes.  Raises
+    ValueError for non-finite input, a motion that is not rigid (max|R^T R - I| > 1e-9) or that rotates by more
+    than a quarter turn per stamp unit."""
+    return _engine(int(device)).deskew(points, stamps, motion, ref)
+
+
+def motion_twist(motion):
+    """The twist Log(motion) of a rigid (dim+1) x (dim+1) motion (gicp_motion_twist, host only): 3-D
+    (w_x, w_y, w_z, v_x, v_y, v_z), 2-D (w, v_x, v_y); ValueError for a motion `deskew` would refuse."""
+    M = np.ascontiguousarray(np.asarray(motion, dtype=np.float64))
+    if M.ndim != 2 or M.shape[0] != M.shape[1] or M.shape[0] not in (3, 4):
+        raise ValueError(f"motion must be 3 x 3 or 4 x 4, got shape {M.shape}")
+    d = M.shape[0] - 1
+    xi = np.empty(3 if d == 2 else 6)
+    check(_lib.load().gicp_motion_twist(d, dptr(M), dptr(xi)), None, "gicp_motion_twist")
+    return xi
+
+
+def deskew_host(points, stamps, motion, ref=0.0):
+    """`deskew` computed on the host by the same per-point function (gicp_deskew_host; no GPU needed)."""
+    a = Engine._cloud(points)
+    _sw, st = Engine._sweep(a, stamps, motion, ref)
+    M = np.ascontiguousarray(np.asarray(motion, dtype=np.float64))
+    out = np.empty_like(a)
+    check(_lib.load().gicp_deskew_host(dptr(a), dptr(st), a.shape[0], a.shape[1], dptr(M), float(ref), dptr(out)), None,
+          "gicp_deskew_host")
+    return out
 
 
 def _devices(device, devices):

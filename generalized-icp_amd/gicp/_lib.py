@@ -109,6 +109,15 @@ class Trace(C.Structure):
     ]
 
 
+class Sweep(C.Structure):
+    """gicp_sweep (include/gicp_hip.h): the stamps, reference stamp and motion of a sweep."""
+    _fields_ = [
+        ("stamps", C.POINTER(C.c_double)),
+        ("ref", C.c_double),
+        ("motion", C.c_double * 16),
+    ]
+
+
 # every entry point include/gicp_hip.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _DP = C.POINTER(C.c_double)
@@ -154,6 +163,13 @@ SIGNATURES = {
     "gicp_set_voxel": (C.c_int, [_VP, C.c_double, C.c_int]),
     "gicp_cloud_size": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_int64)]),
     "gicp_get_points": (C.c_int, [_VP, C.c_int, _DP]),
+    "gicp_motion_twist": (C.c_int, [C.c_int, _DP, _DP]),
+    "gicp_deskew_host": (C.c_int, [_DP, _DP, C.c_int64, C.c_int, _DP, C.c_double, _DP]),
+    "gicp_deskew": (C.c_int, [_VP, _DP, _DP, C.c_int64, C.c_int, _DP, C.c_double, _DP]),
+    "gicp_set_target_sweep": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.POINTER(Params), C.POINTER(Sweep)]),
+    "gicp_set_source_sweep": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.POINTER(Params), C.c_int, C.c_int,
+                                        C.POINTER(Sweep)]),
+    "gicp_stage_target_sweep": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.POINTER(Params), C.c_int, C.POINTER(Sweep)]),
     "gicp_map_reset": (C.c_int, [_VP, C.c_int, C.c_double, C.c_double]),
     "gicp_map_insert": (C.c_int, [_VP, C.c_int, _DP]),
     "gicp_map_insert_points": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, _DP]),
@@ -169,7 +185,7 @@ _lib = None
 
 # the sources gicp_build_info()'s hash covers, in the Makefile's HASH_SRCS order
 HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_voxel.hip",
-             "csrc/gicp_internal.h", "csrc/gicp_mem.h",
+             "csrc/gicp_sweep.hip", "csrc/gicp_internal.h", "csrc/gicp_mem.h", "csrc/gicp_sweep.h",
              "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "../include/gicp_hip.h")
 
 

@@ -19,6 +19,11 @@ Scan-to-map (`map_voxel_size=...`): the engine keeps a local vox
 (`Engine.map_*`); every scan is the source, registered against the map's centroids from the predicted
 sensor pose, then merged into the map at the pose found, and the map becomes the next target.  A
 registration error then moves one scan within the map instead of being integrated into every later pose.
+
+Motion compensation (`deskew=True`): a scan is then N x (dim+1), its last column the per-point
+stamps in units of one sweep ([0, 1) over the sweep), and every scan is de-skewed on the device, as part of its
+build, to the stamp `deskew_ref` (0.5: mid-sweep, so the poses are the sensor's at mid-sweep) under the
+constant-velocity prediction of the sensor's motion over one sweep.
 """
 import math
 import time
@@ -30,7 +35,8 @@ from . import Engine, default_params
 
 class Odometry:
     def __init__(self, dim=3, params=None, device=0, composition="se3", init="constant_velocity", borrow=False,
-                 voxel_size=None, voxel_min_points=1, map_voxel_size=None, map_range=None, map_min_points=1, **kw):
+                 voxel_size=None, voxel_min_points=1, map_voxel_size=None, map_range=None, map_min_points=1,
+                 deskew=False, deskew_ref=0.5, **kw):
         if composition not in ("se3", "reference"):
             raise ValueError("composition must be 'se3' or 'reference'")
         if init not in ("identity", "constant_velocity"):
@@ -62,6 +68,10 @@ class Odometry:
         # borrow=True: staged scans are read by the library in place (GICP_STAGE_BORROW, no copy on this
         # thread); the caller must not modify a scan passed as a coming scan until it has been step()ped
         self.borrow = bool(borrow)
+        # deskew=True: scans carry their stamps as a last column and are de-skewed on the device to the stamp
+        # deskew_ref by the predicted motion over one stamp unit (_predicted_motion)
+        self.deskew = bool(deskew)
+        self.deskew_ref = float(deskew_ref)
         self.reset()
 
     def reset(self):
@@ -84,6 +94,26 @@ class Odometry:
     def _prep(self, scan):
         return np.ascontiguousarray(np.asarray(scan, dtype=np.float64)[:, :self.dim])
 
+    def _predicted_motion(self):
+        """The sensor's motion over one stamp unit, P(tau)^-1 P(tau + 1), as the constant-velocity model
+        predicts it from the registrations known now: scan-to-map P_{k-2}^-1 P_{k-1} of the last two poses,
+        scan-to-scan the inverse of the last registration; the identity while there is none."""
+        if getattr(self, "map_voxel_size", None) is not None:
+            if len(self._poses) >= 2:
+                return np.linalg.inv(self._poses[-2]) @ self._poses[-1]
+        elif self.last_T is not None:
+            return np.linalg.inv(self.last_T)
+        return np.eye(self.dim + 1)
+
+    def _sweep(self, scan):
+        """Engine keywords that make `scan`'s build de-skew it (none with deskew=False)."""
+        if not getattr(self, "deskew", False):
+            return {}
+        a = np.asarray(scan, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != self.dim + 1:
+            raise ValueError(f"with deskew=True a scan is N x {self.dim + 1} (points, then the stamp), got shape {a.shape}")
+        return {"stamps": np.ascontiguousarray(a[:, self.dim]), "motion": self._predicted_motion(), "ref": self.deskew_ref}
+
     def step(self, scan, next_scan=None, next_scans=()):
         """Add one scan; returns (T, result) of its registration against the previous scan, or
         (None, None) for the first frame.  `next_scan` (or the list `next_scans`, at most
@@ -92,6 +122,11 @@ class Odometry:
         before the call returns, so the caller may reuse the array at once; with borrow=True the library
         reads the caller's array in place (no copy on this thread), and the caller must leave it unchanged
         until that scan has itself been step()ped.
+
+        With deskew=True the motion a scan is de-skewed by is predicted when its build starts: for a scan
+        built in this call, from the registrations up to the previous frame; for a staged scan, from the latest
+        registration known when it is staged -- staged `depth` frames ahead, that registration is older by as
+        many frames.
 
         In scan-to-map mode the scan is registered against the map and then merged into it; T is the same
         quantity, P_k^-1 P_{k-1} of the sensor poses, and the coming scans are accepted and ignored."""
@@ -109,7 +144,7 @@ class Odometry:
                 self._staged = []
             if self.frames > 0:
                 self.eng.target_to_source()
-            self.eng.set_target(self._prep(scan), self.params)
+            self.eng.set_target(self._prep(scan), self.params, **self._sweep(scan))
         coming = list(next_scans) if next_scan is None else [next_scan, *next_scans]
         want = coming[:self.eng.MAX_STAGED]
         n_ok = 0                                # staged builds that are a prefix of the coming scans
@@ -119,7 +154,7 @@ class Odometry:
             self.eng.cancel_stage()
             self._staged = []
         for s in want[len(self._staged):]:
-            self.eng.stage_target(self._prep(s), self.params, borrow=self.borrow)
+            self.eng.stage_target(self._prep(s), self.params, borrow=self.borrow, **self._sweep(s))
             self._staged.append(s)
         t1 = time.perf_counter()
         self.timing["setup_s"] += t1 - t0
@@ -137,7 +172,7 @@ class Odometry:
     def _step_map(self, scan):
         t0 = time.perf_counter()
         eng = self.eng
-        eng.set_source(self._prep(scan), self.params)
+        eng.set_source(self._prep(scan), self.params, **self._sweep(scan))
         t1 = time.perf_counter()
         self.timing["setup_s"] += t1 - t0
         self.frames += 1

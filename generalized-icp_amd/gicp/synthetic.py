@@ -424,3 +424,97 @@ def lidar_stream(frames, beams=64, azimuths=1563, seed=7, xp=None, device=None, 
     rng = np.random.default_rng(seed + 1)
     for k in range(frames):
         yield lidar_scan(scene, poses[k], dirs, rng, xp=xp, device=device), poses[k]
+
+
+# ----------------------------------------------------------------------------- skewed sweeps
+# A spinning sensor measures the columns of a sweep one after the other while it moves: every ray of
+# lidar_stream_skewed is cast from the pose the sensor has at that ray's stamp.
+
+def lidar_stamps(beams=64, azimuths=1563):
+    """The stamp of every ray of lidar_dirs(beams, azimuths), in units of one sweep: column j -> j / azimuths."""
+    return np.tile(np.arange(azimuths) / azimuths, beams)
+
+
+def _hat3(w):
+    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+
+
+def _so3_coeffs(th):
+    """(sin th / th, (1 - cos th) / th^2, (th - sin th) / th^3), without cancellation near 0."""
+    if th < 1e-2:
+        t2 = th * th
+        return (1 - t2 / 6 + t2 * t2 / 120, 0.5 - t2 / 24 + t2 * t2 / 720,
+                1 / 6 - t2 / 120 + t2 * t2 / 5040 - t2 ** 3 / 362880)
+    return math.sin(th) / th, 2 * math.sin(th / 2) ** 2 / th ** 2, (th - math.sin(th)) / th ** 3
+
+
+def se3_exp(xi):
+    """4x4 rigid transform Exp(xi) of the twist xi = (w_x, w_y, w_z, v_x, v_y, v_z)."""
+    xi = np.asarray(xi, dtype=np.float64)
+    K = _hat3(xi[:3])
+    A, B, Cc = _so3_coeffs(float(np.linalg.norm(xi[:3])))
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + A * K + B * (K @ K)
+    T[:3, 3] = (np.eye(3) + B * K + Cc * (K @ K)) @ xi[3:]
+    return T
+
+
+def se3_log(T):
+    """The twist (w, v) of a 4x4 rigid transform that turns by less than half a turn: Exp(se3_log(T)) = T."""
+    R = T[:3, :3]
+    a = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    sn = float(np.linalg.norm(a))
+    th = math.atan2(sn, 0.5 * (np.trace(R) - 1.0))
+    w = a * (th / sn) if sn > 0.0 else a
+    K = _hat3(w)
+    _, B, Cc = _so3_coeffs(th)
+    v = np.linalg.solve(np.eye(3) + B * K + Cc * (K @ K), T[:3, 3])
+    return np.concatenate([w, v])
+
+
+def lidar_cast(scene, origins, D, max_range=100.0):
+    """Range of the first hit of every ray (origins[i], unit world direction D[i]) with `scene`; np.inf where
+    there is none within max_range.  The caster of lidar_scan with one origin per ray."""
+    o = np.asarray(origins, dtype=np.float64)
+    best = np.full(len(D), np.inf)
+    for p0, e1, e2 in scene.rects:
+        n = np.cross(e1, e2)
+        dn = D @ n
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = ((p0 - o) @ n) / dn
+        h = o + t[:, None] * D - p0
+        a = (h @ e1) / (e1 @ e1)
+        b = (h @ e2) / (e2 @ e2)
+        ok = (t > 1e-6) & (a >= 0) & (a <= 1) & (b >= 0) & (b <= 1)
+        best = np.where(ok & (t < best), t, best)
+    for cx, cy, cz, r in scene.spheres:
+        oc = o - np.array([cx, cy, cz])
+        bq = np.einsum("ij,ij->i", D, oc)
+        disc = bq * bq - (np.einsum("ij,ij->i", oc, oc) - r * r)
+        sq = np.sqrt(np.maximum(disc, 0))
+        for t in (-bq - sq, -bq + sq):
+            ok = (disc >= 0) & (t > 1e-6) & (t < best)
+            best = np.where(ok, t, best)
+    return np.where(best < max_range, best, np.inf)
+
+
+def lidar_stream_skewed(frames, beams=64, azimuths=1563, seed=7, ref=0.5, noise=0.02, max_range=100.0, **traj):
+    """Generator of (scan_k[N, 4], pose_k) for k = 0..frames-1: sweep k runs from trajectory pose k to pose k + 1
+    at constant twist xi_k = Log(P_k^-1 P_{k+1}), and the ray of stamp tau (lidar_stamps) is cast from the
+    interpolated pose P_k Exp(tau xi_k).  A scan's first three columns are the hits in the sensor frame AT
+    THEIR OWN STAMP (what a spinning sensor reports), the fourth the stamps; pose_k = P_k Exp(ref xi_k) is the
+    sensor pose at stamp `ref`, the frame gicp.deskew(..., ref=ref) moves the scan to.  `traj`: lidar_trajectory
+    keywords."""
+    scene = lidar_scene()
+    poses = lidar_trajectory(frames + 1, seed=seed, **traj)
+    dirs = lidar_dirs(beams, azimuths)
+    stamps = lidar_stamps(beams, azimuths)
+    col = np.tile(np.arange(azimuths), beams)
+    rng = np.random.default_rng(seed + 1)
+    for k in range(frames):
+        xi = se3_log(np.linalg.inv(poses[k]) @ poses[k + 1])
+        P = np.stack([poses[k] @ se3_exp(j / azimuths * xi) for j in range(azimuths)])[col]   # pose of every ray
+        best = lidar_cast(scene, P[:, :3, 3], np.einsum("nij,nj->ni", P[:, :3, :3], dirs), max_range)
+        hit = np.isfinite(best)
+        rng_ = best[hit] + rng.uniform(-noise, noise, hit.sum())
+        yield np.column_stack([dirs[hit] * rng_[:, None], stamps[hit]]), poses[k] @ se3_exp(ref * xi)

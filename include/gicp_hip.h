@@ -156,7 +156,8 @@ typedef struct gicp_debug {
 
 /* ---- library ------------------------------------------------------------ */
 int gicp_version(void);                          /* 100 * major + minor; 101: gicp_params grew by robust_kernel,
-                                                    pad_robust, robust_scale (appended) */
+                                                    pad_robust, robust_scale (appended); 102: motion
+                                                    compensation (gicp_sweep, gicp_deskew, gicp_*_sweep) */
 int gicp_stats_size(int dim);                    /* 26 (dim 2) or 74 (dim 3) */
 void gicp_default_params(int dim, gicp_params* out);
 const char* gicp_strerror(int code);
@@ -201,7 +202,8 @@ int gicp_peer_close(gicp_ctx* ctx);   /* back to no exchange (RCCL / hook as set
 
 /* Build provenance of this library: "src=<first 16 hex of sha256 over the sources>;git=<rev>;built=<date
  * time>;arch=gfx950".  The source hash covers csrc/{gicp_kernels.hip, gicp_capi.cpp, gicp_solver.cpp,
- * gicp_cg.cpp, gicp_voxel.hip, gicp_internal.h, gicp_solver.h, gicp_solve_dev.h} and include/gicp_hip.h, concatenated in that order, so
+ * gicp_cg.cpp, gicp_voxel.hip, gicp_sweep.hip, gicp_internal.h, gicp_mem.h, gicp_sweep.h, gicp_solver.h, gicp_solve_dev.h} and
+ * include/gicp_hip.h, concatenated in that order, so
  * a caller can prove the loaded library was compiled from the sources beside it. */
 const char* gicp_build_info(void);
 
@@ -389,6 +391,54 @@ int gicp_voxel_downsample(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, 
 int gicp_set_voxel(gicp_ctx* ctx, double leaf, int min_points);
 int gicp_cloud_size(gicp_ctx* ctx, int which, int64_t* n);      /* points the indexed cloud holds (0: not set) */
 int gicp_get_points(gicp_ctx* ctx, int which, double* out);     /* [n][dim], the cloud's original order */
+
+/* ---- motion compensation: de-skewing a sweep -----------------------------------------
+ * A SWEEP is a cloud p_i (N x dim, fp64) with one stamp tau_i per point (fp64), a motion M and a reference
+ * stamp ref.  M is a (dim+1)^2 row-major rigid transform: the sensor pose one stamp unit later, expressed in
+ * the sensor frame now, M = P(tau)^-1 P(tau + 1) for sensor -> world poses P.  Stamps in [0, 1) make M the
+ * motion over the sweep, stamps in seconds the motion per second: the library does not care which.  With the
+ * twist xi = Log(M) the de-skewed cloud is
+ *     p'_i = Exp((tau_i - ref) xi) p_i,
+ * the point as seen from the sensor frame at stamp ref, under constant twist.  Twist layout: 3-D
+ * (w_x, w_y, w_z, v_x, v_y, v_z), 2-D (w, v_x, v_y).  Per point, with s = tau_i - ref, phi = s w, u = s v:
+ * p' = R(phi) p + V(phi) u (Rodrigues' formula and its integral); the coefficients switch to their series
+ * below |phi| = 0.1, so the small-angle behaviour is sound ((1 - cos t) / t^2 evaluated naively is 0 at 1e-8).
+ * xi is computed once on the host in fp64, the per-point map runs in fp64, and the same function
+ * (csrc/gicp_sweep.h) serves the device kernel and gicp_deskew_host.  Rows keep their order: "original order"
+ * and "original index" mean what they mean without a sweep.  s = 0 or xi = 0 returns the input.  The last row
+ * of M is not read.
+ * GICP_E_INVALID for: a non-finite M, ref, stamp or coordinate; max|R^T R - I| > 1e-9 or det R <= 0; a rotation
+ * of more than a quarter turn per stamp unit ((tr R - 1) / 2 < 0 in 3-D, R_00 < 0 in 2-D: no constant-velocity
+ * sweep, and Log stays well conditioned); stamps == NULL; a de-skewed cloud that is not finite.
+ *
+ * gicp_motion_twist and gicp_deskew_host are host only, as gicp_solve_pose: no HIP call, no context.
+ * gicp_deskew is the one-shot on the device, host in, host out (out [N][dim] caller-allocated; the context's
+ * clouds are untouched).  Its output is bit-identical from call to call and context to context, and to the
+ * rows a build with the same sweep indexes.
+ * The *_sweep builds are gicp_set_target, gicp_set_source and gicp_stage_target_ex with a sweep (sweep = NULL:
+ * exactly those calls): the cloud is de-skewed on the device after its upload, before the voxel filter (if
+ * set) and the index, which take the device's exact bounds of the de-skewed points (one more stream
+ * synchronisation).  Only the scan and its stamps cross to the device.  gicp_get_points returns the de-skewed
+ * rows (with a filter: their centroids), and gicp_map_insert of the cloud merges them.  A sharded source
+ * de-skews the whole cloud on every rank.  gicp_stage_target_sweep copies the stamps with the points; with
+ * GICP_STAGE_BORROW it reads them in place, under the same lifetime rule.  A sweep refused once the build has
+ * begun (a non-finite stamp, a motion that is not rigid) leaves that cloud NOT SET, as any failed build. */
+typedef struct gicp_sweep {
+    const double* stamps;   /* [N], one per point */
+    double ref;             /* reference stamp: the de-skewed points are in the sensor frame at this stamp */
+    double motion[16];      /* M, (dim+1)^2 values used */
+} gicp_sweep;
+int gicp_motion_twist(int dim, const double* M, double* xi);   /* xi[6] (3-D) or xi[3] (2-D) = Log(M), and the checks */
+int gicp_deskew_host(const double* xyz, const double* stamps, int64_t N, int dim, const double* M, double ref,
+                     double* out);
+int gicp_deskew(gicp_ctx* ctx, const double* xyz, const double* stamps, int64_t N, int dim, const double* M,
+                double ref, double* out);
+int gicp_set_target_sweep(gicp_ctx* ctx, const double* xyz, int64_t M, int dim, const gicp_params* p,
+                          const gicp_sweep* sweep);
+int gicp_set_source_sweep(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, const gicp_params* p, int shard,
+                          int nshards, const gicp_sweep* sweep);
+int gicp_stage_target_sweep(gicp_ctx* ctx, const double* xyz, int64_t M, int dim, const gicp_params* p, int flags,
+                            const gicp_sweep* sweep);
 
 /* ---- local voxel map ----------------------------------------------------------------
  * A device-resident set of voxels of the same absolute grid as the filter above, in the WORLD frame: each

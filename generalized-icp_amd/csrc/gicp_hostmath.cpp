@@ -1,0 +1,438 @@
+// gicp_hostmath.cpp — host arithmetic of the library with no HIP call in it (gicp_hostmath.h).
+#include "gicp_hostmath.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <type_traits>
+
+#include "gicp_sweep.h"
+
+namespace gicp {
+
+void default_params(int dim, gicp_params* p) {
+    std::memset(p, 0, sizeof(*p));
+    p->max_iterations = 100;
+    p->k_neighbors = dim == 2 ? 6 : 20;
+    p->tolerance = 1e-6;
+    p->max_distance_correspondence = 150.0;
+    p->max_distance_nearest_neighbors = 50.0;
+    p->epsilon = 100.0;
+    p->ratio = 0.1;
+    p->fixed_iterations = 0;
+    p->min_neighbors = dim;
+}
+
+gicp_params resolve(int dim, const gicp_params* in) {
+    gicp_params p;
+    default_params(dim, &p);
+    if (!in) return p;
+    p = *in;
+    if (p.k_neighbors <= 0) p.k_neighbors = dim == 2 ? 6 : 20;
+    if (p.min_neighbors <= 0) p.min_neighbors = dim;
+    if (p.epsilon == 0.0) p.epsilon = 100.0;
+    if (p.cov_model < GICP_COV_PLANE_TO_PLANE || p.cov_model > GICP_COV_POINT_TO_PLANE)
+        throw Fail{GICP_E_INVALID, "cov_model must be GICP_COV_PLANE_TO_PLANE, _POINT_TO_POINT or _POINT_TO_PLANE"};
+    if (p.robust_kernel < GICP_ROBUST_NONE || p.robust_kernel > GICP_ROBUST_TUKEY)
+        throw Fail{GICP_E_INVALID, "robust_kernel must be GICP_ROBUST_NONE, _HUBER, _CAUCHY, _GEMAN_MCCLURE or _TUKEY"};
+    if (p.robust_kernel != GICP_ROBUST_NONE && !(std::isfinite(p.robust_scale) && p.robust_scale > 0.0))
+        throw Fail{GICP_E_INVALID, "robust_scale must be finite and > 0 with a robust kernel"};
+    if (p.rotation_epsilon <= 0.0 && p.transformation_epsilon > 0.0) p.rotation_epsilon = 1.0 - p.transformation_epsilon;
+    return p;
+}
+
+// fp32-screen error bound: E bounds the error of one coordinate difference
+Margin make_margin(int dim, float rho_q, float rho_db, double dmax) {
+    const double E = std::ldexp(8.0 * rho_q + 3.0 * rho_db + 3.0 * dmax, -23) + 1e-30;
+    Margin m;
+    m.a = (float)(2.0 * std::sqrt((double)dim) * E);
+    m.b = (float)(dim * E * E);
+    m.c = (float)std::ldexp(1.0, -16);
+    return m;
+}
+float screen_bound(const Margin& m, double d) {
+    const double d2 = d * d;
+    const double b = d2 + 2.0 * (m.a * d + m.b + m.c * d2);
+    return (float)(b * (1.0 + 1e-6)) + 1e-30f;
+}
+
+// The largest double x with sqrt(x) <= dc (sqrt correctly rounded, as on the device), so the accept
+// test of gicp.py:136, !(distance > d_c) with distance = sqrt(d2), is exactly d2 <= accept_d2_max(d_c)
+double accept_d2_max(double dc) {
+    if (!(dc >= 0.0) || std::isinf(dc)) return dc;   // d_c = +inf accepts everything; NaN nothing
+    double x = dc * dc;
+    while (std::sqrt(x) > dc) x = std::nextafter(x, 0.0);
+    while (std::sqrt(std::nextafter(x, INFINITY)) <= dc) x = std::nextafter(x, INFINITY);
+    return x;
+}
+
+// Cut the Morton-sorted points into tiles: runs of <= 64 consecutive points whose bounding box (in
+// Morton grid cells) stays within an extent cap E.  E is the smallest cap (steps of 2^(1/4)) whose
+// tile count stays <= 1.35x the minimum ceil(n/64): tiles are as compact as that budget allows, and
+// the cap bounds the largest tile, which sets both the widest query wave and the loosest box.
+void build_tile_table(const std::vector<uint32_t>& codes, int dim, int bits, std::vector<int32_t>& start,
+                      std::vector<int32_t>& count, std::vector<uint32_t>& first_code, int& cap_out, int k_hint,
+                      WorkerPool& pool, int maxp) {
+    const int64_t n = (int64_t)codes.size();
+    static const double budget = [] {   // GICP_TILE_BUDGET: tile-count budget over ceil(n / 64)
+        const char* e = std::getenv("GICP_TILE_BUDGET");
+        const double b = e ? std::atof(e) : 1.35;
+        return b >= 1.0 ? b : 1.35;
+    }();
+    const int64_t target = (int64_t)(budget * std::ceil(n / (double)maxp)) + 2;   // (maxp <= 64 points a tile)
+    // decode the grid coordinates once
+    auto compact3 = [](uint32_t x) {   // inverse of the kernels' spread3
+        x &= 0x09249249u;
+        x = (x | (x >> 2)) & 0x030C30C3u;
+        x = (x | (x >> 4)) & 0x0300F00Fu;
+        x = (x | (x >> 8)) & 0x030000FFu;
+        x = (x | (x >> 16)) & 0x000003FFu;
+        return x;
+    };
+    auto compact2 = [](uint32_t x) {
+        x &= 0x55555555u;
+        x = (x | (x >> 1)) & 0x33333333u;
+        x = (x | (x >> 2)) & 0x0F0F0F0Fu;
+        x = (x | (x >> 4)) & 0x00FF00FFu;
+        x = (x | (x >> 8)) & 0x0000FFFFu;
+        return x;
+    };
+    std::vector<uint16_t> g((size_t)n * dim);
+    constexpr int kSeg = 16;   // fixed segments (independent of the host's core count: deterministic)
+    pool.run(kSeg, [&](int k) {
+        for (int64_t i = n * k / kSeg; i < n * (k + 1) / kSeg; ++i) {
+            const uint32_t c = codes[i];
+            for (int a = 0; a < dim; ++a)
+                g[(size_t)i * dim + a] = (uint16_t)(dim == 3 ? compact3(c >> a) : compact2(c >> a));
+        }
+    });
+    // greedy cut of points [b, e) (a forced break at b); appends (start, count) pairs if `out`
+    auto cut_seg = [&](int64_t b, int64_t e, int E, std::vector<int32_t>* out) -> int64_t {
+        int64_t nt = 0, i0 = b;
+        int lo0 = 0, lo1 = 0, lo2 = 0, hi0 = 0, hi1 = 0, hi2 = 0;
+        const uint16_t* gp = g.data();
+        for (int64_t i = b; i < e; ++i) {
+            const int v0 = gp[i * dim], v1 = gp[i * dim + 1], v2 = dim == 3 ? gp[i * dim + 2] : 0;
+            if (i > i0) {
+                const int n0 = std::min(lo0, v0), x0 = std::max(hi0, v0);
+                const int n1 = std::min(lo1, v1), x1 = std::max(hi1, v1);
+                const int n2 = std::min(lo2, v2), x2 = std::max(hi2, v2);
+                if (i - i0 < maxp && x0 - n0 <= E && x1 - n1 <= E && x2 - n2 <= E) {
+                    lo0 = n0, hi0 = x0, lo1 = n1, hi1 = x1, lo2 = n2, hi2 = x2;
+                    continue;
+                }
+                ++nt;
+                if (out) {
+                    out->push_back((int32_t)i0);
+                    out->push_back((int32_t)(i - i0));
+                }
+                i0 = i;
+            }
+            lo0 = hi0 = v0, lo1 = hi1 = v1, lo2 = hi2 = v2;
+        }
+        if (e > i0) {
+            ++nt;
+            if (out) {
+                out->push_back((int32_t)i0);
+                out->push_back((int32_t)(e - i0));
+            }
+        }
+        return nt;
+    };
+    // the 16 segments are cut concurrently on the pool
+    std::vector<std::vector<int32_t>> seg_out(kSeg);
+    auto cut = [&](int E, bool emit) -> int64_t {
+        int64_t nt_seg[kSeg] = {};
+        pool.run(kSeg, [&](int k) {
+            if (emit) seg_out[k].clear();
+            nt_seg[k] = cut_seg(n * k / kSeg, n * (k + 1) / kSeg, E, emit ? &seg_out[k] : nullptr);
+        });
+        int64_t nt = 0;
+        for (int k = 0; k < kSeg; ++k) nt += nt_seg[k];
+        if (emit)
+            for (int k = 0; k < kSeg; ++k)
+                for (size_t j = 0; j < seg_out[k].size(); j += 2) {
+                    start.push_back(seg_out[k][j]);
+                    count.push_back(seg_out[k][j + 1]);
+                    first_code.push_back(codes[seg_out[k][j]]);
+                }
+        return nt;
+    };
+    // smallest cap on the grid E_k = 2 * 2^(k/4) meeting the budget (the count falls as E grows):
+    // a short walk from the previous cloud's k when given (a frame stream changes little), else a
+    // binary search over k
+    const auto cap_of = tile_cap_of;
+    const int kmax = 4 * (bits - 1);   // cap_of(kmax) = 2^bits: one Morton run per tile
+    int klo = 0, khi = kmax;
+    if (k_hint > 0 && k_hint < kmax) {   // walk from the hint: usually hint feasible, hint-1 not
+        if (cut(cap_of(k_hint), false) <= target) {
+            khi = k_hint;
+            klo = k_hint - 1;
+            if (cut(cap_of(klo), false) <= target) {
+                khi = klo;
+                klo = 0;
+            } else {
+                klo = k_hint;
+            }
+        } else {
+            klo = k_hint + 1;
+        }
+    }
+    while (klo < khi) {
+        const int km = (klo + khi) / 2;
+        if (cut(cap_of(km), false) <= target) khi = km;
+        else klo = km + 1;
+    }
+    const int E = cap_of(klo);
+    cap_out = klo;
+    start.clear();
+    count.clear();
+    first_code.clear();
+    cut(E, true);
+}
+
+// Tiles of shard `shard` of `nshards` (the k_corr split: chunks of kShardChunk units of kCorrWaves tiles, dealt
+// round-robin), or all of them when nshards = 1.
+int shard_tile_count(int ntiles, int shard, int nshards) {
+    if (nshards <= 1) return ntiles;
+    constexpr int kChunkTiles = kShardChunk * kCorrWaves;
+    const int nchunks = (ntiles + kChunkTiles - 1) / kChunkTiles;
+    int mine = 0;
+    for (int c = shard; c < nchunks; c += nshards) mine += std::min(kChunkTiles, ntiles - c * kChunkTiles);
+    return mine;
+}
+
+// Morton seed lookup (DevCloud::seed_tab) over the tiles' first codes: 2^sb buckets of the code's top bits, about
+// 4 per tile, and one closing entry.  Returns the shift that takes a code to its bucket (DevCloud::seed_shift).
+int build_seed_table(const std::vector<uint32_t>& tcode, int code_bits, std::vector<int32_t>& seed) {
+    const int ntiles = (int)tcode.size();
+    int sb = 2;
+    while ((1 << sb) < 4 * ntiles && sb < 20) ++sb;
+    sb = std::min(sb, code_bits);
+    const int shift = code_bits - sb;
+    const size_t nb = (size_t)1 << sb;
+    seed.resize(nb + 1);
+    int t = 0;   // last tile whose first code <= p << shift (0 if none)
+    for (size_t p = 0; p < nb; ++p) {
+        const uint64_t lim = (uint64_t)p << shift;
+        while (t + 1 < ntiles && (uint64_t)tcode[t + 1] <= lim) ++t;
+        seed[p] = t;
+    }
+    seed[nb] = ntiles - 1;
+    return shift;
+}
+
+// Bounds of a host cloud and its finiteness test in one fused, branch-free pass (v - v is NaN for NaN and +-inf).
+void scan_bounds(const double* xyz, int64_t n, int dim, double (&mn)[3], double (&mx)[3]) {
+    for (int a = 0; a < 3; ++a) mn[a] = mx[a] = 0.0;
+    bool finite = true;
+    auto scan = [&](auto D_) {
+        constexpr int D = decltype(D_)::value;
+        double lo[D], hi[D], acc[D];
+        for (int a = 0; a < D; ++a) lo[a] = hi[a] = xyz[a], acc[a] = 0.0;
+        for (int64_t i = 0; i < n; ++i)
+            for (int a = 0; a < D; ++a) {
+                const double v = xyz[i * D + a];
+                lo[a] = v < lo[a] ? v : lo[a];
+                hi[a] = v > hi[a] ? v : hi[a];
+                acc[a] += v - v;
+            }
+        for (int a = 0; a < D; ++a) {
+            mn[a] = lo[a], mx[a] = hi[a];
+            finite = finite && acc[a] == 0.0 && std::isfinite(lo[a]) && std::isfinite(hi[a]);
+        }
+    };
+    if (dim == 3) scan(std::integral_constant<int, 3>{});
+    else scan(std::integral_constant<int, 2>{});
+    if (!finite) throw Fail{GICP_E_INVALID, "cloud contains non-finite coordinates"};
+}
+
+// the finiteness test of a sweep's stamps and reference stamp (v - v is NaN for NaN and +-inf)
+void scan_stamps(const double* stamps, int64_t n, double ref) {
+    if (!std::isfinite(ref)) throw Fail{GICP_E_INVALID, "sweep reference stamp is not finite"};
+    double acc = 0.0;
+    for (int64_t i = 0; i < n; ++i) acc += stamps[i] - stamps[i];
+    if (!(acc == 0.0)) throw Fail{GICP_E_INVALID, "sweep contains non-finite stamps"};
+}
+
+// doubles from the ordered-integer form gicp_voxel.hip reduces min / max in
+double dec_ordered(unsigned long long e) {
+    const unsigned long long b = (e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
+    double v;
+    std::memcpy(&v, &b, sizeof v);
+    return v;
+}
+
+// the bounds in the result words of a device reduction (gicp_internal.h kVoxelRes): min[3], then max[3]
+void decode_bounds(const unsigned long long* res, int dim, double (&mn)[3], double (&mx)[3]) {
+    for (int a = 0; a < 3; ++a) mn[a] = mx[a] = 0.0;
+    for (int a = 0; a < dim; ++a) {
+        mn[a] = dec_ordered(res[a]);
+        mx[a] = dec_ordered(res[3 + a]);
+    }
+}
+
+// The voxel filter's lowest cell per axis and key bits: division by a positive leaf is monotone, so every point's
+// cell lies in [floor(min / leaf), floor(max / leaf)], computed here as the device computes it.  Returns the
+// bits the sort covers (>= 1).
+int voxel_key_bits(int dim, const double (&mn)[3], const double (&mx)[3], double leaf, double (&cmin)[3], int32_t (&bits)[3]) {
+    const double lim = dim == 3 ? 2097152.0 : 2147483648.0;   // 2^21, 2^31 cells per axis
+    int total = 0;
+    for (int a = 0; a < dim; ++a) {
+        const double c0 = std::floor(mn[a] / leaf), c1 = std::floor(mx[a] / leaf);
+        const double range = c1 - c0 + 1.0;
+        if (!(std::fabs(c0) < 4503599627370496.0 && std::fabs(c1) < 4503599627370496.0 && range <= lim)) {
+            char b[160];
+            std::snprintf(b, sizeof b, "voxel grid too wide: axis %d spans %.6g cells of leaf %g (at most 2^%d per axis in %d-D)",
+                          a, range, leaf, dim == 3 ? 21 : 31, dim);
+            throw Fail{GICP_E_INVALID, b};
+        }
+        cmin[a] = c0;
+        uint64_t r = (uint64_t)range - 1;
+        int nb = 0;
+        while (r) ++nb, r >>= 1;
+        bits[a] = nb;
+        total += nb;
+    }
+    return std::max(1, total);
+}
+
+// The local map's window: its half-width R in cells, and the key bits per axis ceil(log2(2 R + 1))
+int64_t map_window_cells(int dim, double leaf, double max_range, int& bits) {
+    const double R = std::ceil(max_range / leaf);
+    const double lim = dim == 3 ? 2097152.0 : 2147483648.0;   // 2^21, 2^31 cells per axis (the filter's limits)
+    if (!(2.0 * R + 1.0 <= lim)) {
+        char b[160];
+        std::snprintf(b, sizeof b, "map window too wide: %.6g cells of leaf %g per axis (at most 2^%d per axis in %d-D)",
+                      2.0 * R + 1.0, leaf, dim == 3 ? 21 : 31, dim);
+        throw Fail{GICP_E_INVALID, b};
+    }
+    uint64_t r = (uint64_t)(2 * (int64_t)R);
+    bits = 0;
+    while (r) ++bits, r >>= 1;
+    return (int64_t)R;
+}
+
+// ... and its lowest cell on `axis` when centred on the coordinate t
+int64_t map_window_lo(int axis, double t, double leaf, int64_t R) {
+    const double c = std::floor(t / leaf);   // the centre cell
+    if (!(std::fabs(c) + (double)R < 2147483648.0)) {
+        char b[160];
+        std::snprintf(b, sizeof b, "map window leaves the int32 cell range: axis %d is centred on cell %.6g with a half-width of %lld cells",
+                      axis, c, (long long)R);
+        throw Fail{GICP_E_INVALID, b};
+    }
+    return (int64_t)c - R;
+}
+
+// ---- motion compensation (gicp_sweep.h) ----
+
+// The twist xi = Log(M) of a rigid motion M ((dim+1)^2 row-major, last row not read): 3-D (omega[3], v[3]),
+// 2-D (omega, v[2]).  Refuses what is no constant-velocity sweep: a non-finite M, a linear part that is no
+// rotation, more than a quarter turn per stamp unit (which also keeps Log well conditioned: theta <= pi / 2).
+void motion_twist(int dim, const double* M, double* xi) {
+    if (dim != 2 && dim != 3) throw Fail{GICP_E_INVALID, "dim must be 2 or 3"};
+    if (!M || !xi) throw Fail{GICP_E_INVALID, "motion and twist must not be NULL"};
+    const int w = dim + 1;
+    double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}}, t[3] = {0, 0, 0};
+    for (int r = 0; r < dim; ++r) {
+        for (int c = 0; c < w; ++c)
+            if (!std::isfinite(M[r * w + c])) throw Fail{GICP_E_INVALID, "motion contains non-finite values"};
+        for (int c = 0; c < dim; ++c) R[r][c] = M[r * w + c];
+        t[r] = M[r * w + dim];
+    }
+    double dev = 0.0;
+    for (int a = 0; a < dim; ++a)
+        for (int b = 0; b < dim; ++b) {
+            double g = a == b ? -1.0 : 0.0;
+            for (int k = 0; k < dim; ++k) g += R[k][a] * R[k][b];
+            dev = std::max(dev, std::fabs(g));
+        }
+    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) - R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+    if (!(dev <= 1e-9) || !(det > 0.0)) {
+        char b[128];
+        std::snprintf(b, sizeof b, "motion is not rigid: max|R^T R - I| = %.3g (at most 1e-9), det R = %.3g", dev, det);
+        throw Fail{GICP_E_INVALID, b};
+    }
+    const char* turn = "motion rotates by more than a quarter turn per stamp unit";
+    double A, B, C;
+    if (dim == 3) {
+        const double cs = 0.5 * (R[0][0] + R[1][1] + R[2][2] - 1.0);
+        if (cs < 0.0) throw Fail{GICP_E_INVALID, turn};
+        // a = sin(theta) axis, from the skew part; theta = atan2(|a|, cos(theta)) is accurate at every angle
+        const double a[3] = {0.5 * (R[2][1] - R[1][2]), 0.5 * (R[0][2] - R[2][0]), 0.5 * (R[1][0] - R[0][1])};
+        const double sn = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+        const double f = sn > 0.0 ? std::atan2(sn, cs) / sn : 1.0;
+        const double o[3] = {f * a[0], f * a[1], f * a[2]};
+        sweep_coeffs(o[0] * o[0] + o[1] * o[1] + o[2] * o[2], A, B, C);
+        // v solves V v = t, V = I + B o^ + C o^2 (o^2 = o o^T - |o|^2 I)
+        const double K[3][3] = {{0, -o[2], o[1]}, {o[2], 0, -o[0]}, {-o[1], o[0], 0}};
+        double V[3][3];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) {
+                double k2 = 0.0;
+                for (int k = 0; k < 3; ++k) k2 += K[r][k] * K[k][c];
+                V[r][c] = (r == c ? 1.0 : 0.0) + B * K[r][c] + C * k2;
+            }
+        const double c00 = V[1][1] * V[2][2] - V[1][2] * V[2][1], c01 = V[1][2] * V[2][0] - V[1][0] * V[2][2],
+                     c02 = V[1][0] * V[2][1] - V[1][1] * V[2][0];
+        const double dV = V[0][0] * c00 + V[0][1] * c01 + V[0][2] * c02;
+        const double inv[3][3] = {
+            {c00, V[0][2] * V[2][1] - V[0][1] * V[2][2], V[0][1] * V[1][2] - V[0][2] * V[1][1]},
+            {c01, V[0][0] * V[2][2] - V[0][2] * V[2][0], V[0][2] * V[1][0] - V[0][0] * V[1][2]},
+            {c02, V[0][1] * V[2][0] - V[0][0] * V[2][1], V[0][0] * V[1][1] - V[0][1] * V[1][0]}};
+        for (int r = 0; r < 3; ++r) {
+            xi[r] = o[r];
+            xi[3 + r] = (inv[r][0] * t[0] + inv[r][1] * t[1] + inv[r][2] * t[2]) / dV;
+        }
+    } else {
+        if (R[0][0] < 0.0) throw Fail{GICP_E_INVALID, turn};
+        const double o = std::atan2(R[1][0] - R[0][1], R[0][0] + R[1][1]);
+        sweep_coeffs(o * o, A, B, C);
+        // V = (A  -B o; B o  A)
+        const double Bo = B * o, dV = A * A + Bo * Bo;
+        xi[0] = o;
+        xi[1] = (A * t[0] + Bo * t[1]) / dV;
+        xi[2] = (A * t[1] - Bo * t[0]) / dV;
+    }
+}
+
+void deskew_host(const double* xyz, const double* stamps, int64_t n, int dim, const double* xi, double ref, double* out) {
+    if (dim == 3)
+        for (int64_t i = 0; i < n; ++i) sweep_point<3>(xi, stamps[i] - ref, xyz + i * 3, out + i * 3);
+    else
+        for (int64_t i = 0; i < n; ++i) sweep_point<2>(xi, stamps[i] - ref, xyz + i * 2, out + i * 2);
+}
+
+// ---- what every entry point checks the same way ----
+
+void check_cloud_args(const double* xyz, int64_t n, int dim) {
+    if (!xyz || n <= 0 || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cloud must be a non-empty N x 2 or N x 3 array"};
+    if (n > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cloud too large (> 2^31 points)"};
+}
+
+void check_shard(int shard, int nshards) {
+    if (nshards < 1 || shard < 0 || shard >= nshards) throw Fail{GICP_E_INVALID, "bad shard / nshards"};
+}
+
+// The exception in flight (call inside a catch block) as a GICP_E_* code and its text; the callers add their prefix.
+int current_failure(std::string& msg) {
+    try {
+        throw;
+    } catch (const Fail& f) {
+        msg = f.msg;
+        return f.code;
+    } catch (const std::bad_alloc&) {
+        msg = "out of host memory";
+        return GICP_E_NOMEM;
+    } catch (...) {
+        msg = "unknown error";
+        return GICP_E_INVALID;
+    }
+}
+
+}  // namespace gicp

@@ -184,9 +184,11 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, _DP, C.c_int, C.c_void_p)
 _lib = None
 
 # the sources gicp_build_info()'s hash covers, in the Makefile's HASH_SRCS order
-HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_voxel.hip",
+HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
+             "csrc/gicp_build.cpp", "csrc/gicp_align.cpp", "csrc/gicp_exchange.cpp", "csrc/gicp_voxel.hip",
              "csrc/gicp_sweep.hip", "csrc/gicp_internal.h", "csrc/gicp_mem.h", "csrc/gicp_sweep.h",
-             "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "../include/gicp_hip.h")
+             "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
+             "../include/gicp_hip.h")
 
 
 def source_hash():

@@ -6,31 +6,16 @@ the address and undefined-behaviour sanitizers (LeakSanitizer included) and run 
 policy, failure injection, moves and swaps, allocate-initialise-publish, and no leak at exit.  No GPU and
 nothing loaded into Python."""
 import os
-import shutil
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from native_build import ROOT, build
+
 SRC = os.path.join(ROOT, "tests", "native", "mem_check.cpp")
 CASES = ("growth_policy_device", "growth_policy_pinned", "failure_injection", "moves_and_swaps", "publish_after_init")
 
 
-def host_compiler():
-    """The host compiler of the ROCm tree the library is built with (the Makefile's ROCM), or g++."""
-    clang = os.path.join(os.environ.get("ROCM", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
-    cxx = clang if os.access(clang, os.X_OK) else shutil.which("g++")
-    assert cxx, "no host C++ compiler: neither the ROCm tree's clang++ nor g++"
-    return cxx
-
-
 def test_owning_buffers_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "mem_check")
-    cxx = host_compiler()
-    cmd = [cxx, "-std=c++17", "-Wall", "-Werror", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-           SRC, "-o", exe]
-    if os.path.basename(cxx) == "g++":   # clang links the sanitizer runtimes statically by default; g++ on request
-        cmd[1:1] = ["-static-libasan", "-static-libubsan"]
-    built = subprocess.run(cmd, capture_output=True, text=True)
-    assert built.returncode == 0, built.stderr
+    exe = build([SRC], str(tmp_path / "mem_check"), "address,undefined", ["-fno-sanitize-recover=all"])
     run = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     print(run.stdout)
     assert run.returncode == 0, (run.stdout, run.stderr)

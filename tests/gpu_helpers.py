@@ -1,6 +1,7 @@
-"""Helpers shared by the GPU tests that drive engines directly (test_gpu_edges.py, test_gpu_history.py):
-engines created under GICP_* switches, one pass against the oracle, the covariance criteria, and the small
-input builders both files use.  References: the oracle (cKDTree, fp64) and tests/edge_ref.py."""
+"""Helpers shared by the GPU tests that drive engines directly (test_gpu_edges.py, test_gpu_history.py,
+test_gpu_density.py): engines created under GICP_* switches, one pass against the oracle, the covariance
+criteria, the graph rows' coverage, and the small input builders the files share.  References: the oracle
+(cKDTree, fp64) and tests/edge_ref.py."""
 import numpy as np
 import pytest
 
@@ -8,6 +9,7 @@ import edge_ref as E
 from oracle import gicp_oracle as O
 
 gicp = pytest.importorskip("gicp")
+from gicp import _lib  # noqa: E402
 from gicp import synthetic as S  # noqa: E402
 
 P3 = dict(max_distance_correspondence=0.5, max_distance_nearest_neighbors=1.0)
@@ -101,6 +103,35 @@ def check_covariances(eng, pts, d_n, which="target", max_left_out=0.02, **kw):
         assert rep["entry_err"][wide].max(initial=0.0) <= 1e-8, rep["entry_err"][wide].max()
     assert np.all(rep["entry_err"][~surf] == 0)
     return rep
+
+
+def graph_rows_cover_their_radius(pts, idx, rad):
+    """The property of test_target_graph_rows_cover_their_radius for EVERY row, by brute force in fp64: rows
+    hold distinct other points, real entries first, nearest first; every other point strictly inside radius[i]
+    is in row i.  (A row whose ties overflowed has radius 0 and covers nothing: test_graph_rows_on_the_lattice.)"""
+    n = len(pts)
+    assert idx.shape == (n, _lib.GRAPH_K) and rad.shape == (n,)
+    assert np.all(np.isfinite(rad)) and np.all(rad >= 0)
+    assert np.all((idx >= -1) & (idx < n))
+    real = idx >= 0
+    assert np.all(real[:, :-1] >= real[:, 1:])                      # real entries first, then the -1 pads
+    for lo in range(0, n, 512):
+        rows = np.arange(lo, min(n, lo + 512))
+        d2 = np.zeros((len(rows), n))
+        for a in range(pts.shape[1]):
+            d2 += (pts[rows, a][:, None] - pts[None, :, a]) ** 2
+        d2[np.arange(len(rows)), rows] = np.inf
+        inrow = np.zeros((len(rows), n + 1), dtype=np.int32)
+        np.add.at(inrow, (np.arange(len(rows))[:, None], np.where(real[rows], idx[rows], n)), 1)
+        inrow = inrow[:, :n]
+        assert inrow.max(initial=0) <= 1, "a row holds a point twice"
+        assert not np.any(inrow[np.arange(len(rows)), rows]), "a row holds its own point"
+        missing = (d2 < (rad[rows] ** 2)[:, None]) & (inrow == 0)
+        assert not np.any(missing), (int(missing.sum()), rows[np.nonzero(missing.any(axis=1))[0][:5]])
+        d = np.sqrt(np.take_along_axis(d2, np.where(real[rows], idx[rows], rows[:, None]), axis=1))
+        d = np.where(real[rows], d, 0.0)                               # (the pads' entries are not compared)
+        both = real[rows][:, 1:]                                       # (real entries come first)
+        assert np.all(np.diff(d, axis=1)[both] >= -1e-6 * (1.0 + d[:, 1:][both])), "not nearest first"
 
 
 def planar_lattice(seed=3):

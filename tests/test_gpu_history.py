@@ -24,6 +24,7 @@ import sys
 import numpy as np
 import pytest
 
+import density_ref as D
 import edge_ref as E
 import gpu_helpers as G
 from oracle import gicp_oracle as O
@@ -323,35 +324,6 @@ def build_by(e, path, pts, p):
     e.commit_target()
 
 
-def graph_rows_cover_their_radius(pts, idx, rad):
-    """The property of test_target_graph_rows_cover_their_radius for EVERY row, by brute force in fp64: rows
-    hold distinct other points, real entries first, nearest first; every other point strictly inside radius[i]
-    is in row i.  (A row whose ties overflowed has radius 0 and covers nothing: test_graph_rows_on_the_lattice.)"""
-    n = len(pts)
-    assert idx.shape == (n, _lib.GRAPH_K) and rad.shape == (n,)
-    assert np.all(np.isfinite(rad)) and np.all(rad >= 0)
-    assert np.all((idx >= -1) & (idx < n))
-    real = idx >= 0
-    assert np.all(real[:, :-1] >= real[:, 1:])                      # real entries first, then the -1 pads
-    for lo in range(0, n, 512):
-        rows = np.arange(lo, min(n, lo + 512))
-        d2 = np.zeros((len(rows), n))
-        for a in range(pts.shape[1]):
-            d2 += (pts[rows, a][:, None] - pts[None, :, a]) ** 2
-        d2[np.arange(len(rows)), rows] = np.inf
-        inrow = np.zeros((len(rows), n + 1), dtype=np.int32)
-        np.add.at(inrow, (np.arange(len(rows))[:, None], np.where(real[rows], idx[rows], n)), 1)
-        inrow = inrow[:, :n]
-        assert inrow.max(initial=0) <= 1, "a row holds a point twice"
-        assert not np.any(inrow[np.arange(len(rows)), rows]), "a row holds its own point"
-        missing = (d2 < (rad[rows] ** 2)[:, None]) & (inrow == 0)
-        assert not np.any(missing), (int(missing.sum()), rows[np.nonzero(missing.any(axis=1))[0][:5]])
-        d = np.sqrt(np.take_along_axis(d2, np.where(real[rows], idx[rows], rows[:, None]), axis=1))
-        d = np.where(real[rows], d, 0.0)                               # (the pads' entries are not compared)
-        both = real[rows][:, 1:]                                       # (real entries come first)
-        assert np.all(np.diff(d, axis=1)[both] >= -1e-6 * (1.0 + d[:, 1:][both])), "not nearest first"
-
-
 def _lattice_checks(e, pts, d_n, dim):
     cnt = e.neighbor_counts("target")
     _, cnt_or = O.covariances(pts, d_n, 20 if dim == 3 else 10)
@@ -479,13 +451,21 @@ def _edge_clouds():
             patch = E.dense_patch(dim, n, n)[1]
             out[f"size_{n}_{dim}d"] = (patch, G.ladder_params(dim),
                                        lambda e, patch=patch: G.check_covariances(e, patch, 1.0, "target"))
+    # clouds whose grid the build cannot resolve (tests/density_ref.py): one cell for the whole core, tiles
+    # kilometres wide around a dense core
+    for name in DENSITY_CLOUDS:
+        f = D.fixture(name)
+        pd = gicp.default_params(f["dim"], **D.params_kw(f))
+        out[name] = (f["target"], pd, lambda e, f=f, name=name: G.check_covariances(
+            e, f["target"], f["d_n"], "target", max_left_out=D.max_left_out(name, "target")))
     return out
 
 
+DENSITY_CLOUDS = ["stretched_3d", "halo_3d", "stretched_2d"]
 EDGE_CLOUDS = ["lattice_3d_dn_1.0", "lattice_3d_dn_above_1.0", "lattice_2d_dn_1.0", "lattice_2d_dn_above_1.0",
                "tied_kth_3d", "collinear_3d", "collinear_2d", "coincident_3d", "coincident_2d"] + [f"size_{n}_{d}d" for d in (3, 2)
                                                                      for n in (1, 63, 64, 65, 129)] + ["size_4000_3d",
-                                                                                                       "size_4000_2d"]
+                                                                                                       "size_4000_2d"] + DENSITY_CLOUDS
 
 
 @pytest.fixture(scope="module")
@@ -530,7 +510,7 @@ def test_every_build_path_agrees(path_engine, edge_clouds, cloud):
         assert e.n_tgt == len(pts)
         check(e)
         idx, rad = e.graph()
-        graph_rows_cover_their_radius(pts, idx, rad)
+        G.graph_rows_cover_their_radius(pts, idx, rad)
         got[path] = (e.covariances("target"), e.neighbor_counts("target"), rad)
     ref = got["set_target"]
     for path in PATHS[1:]:

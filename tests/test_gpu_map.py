@@ -154,6 +154,59 @@ def test_window_forgets_and_starts_again(eng, leaf, max_range, dim):
     assert np.all(again[kept] >= 2 * first[2][kept])
 
 
+# 4b --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dim", [3, 2])
+def test_widest_accepted_window(eng, dim):
+    """Leaf 1.0 and max_range 2^20 - 1 (3-D) or 2^30 - 1 (2-D): 2 R + 1 = 2^21 - 1 or 2^31 - 1 cells per axis,
+    the widest accepted window (63 and 62 key bits); one more is refused.  An insert centred on a negative cell
+    with points (at cell + 0.5, exact in fp64) in the window's lowest and highest corner cells, in the cells
+    next to them, one cell outside on either side of every axis, 70 in one cell and 2000 scattered; a second
+    insert re-centres by one cell on every axis, so the lowest corner voxel is forgotten and the cell beyond the
+    highest corner is now inside.  Cells and counts exactly map_ref's, centroids within its bound."""
+    R = 2 ** 20 - 1 if dim == 3 else 2 ** 30 - 1
+    with pytest.raises(ValueError, match="window too wide"):
+        eng.map_reset(1.0, float(R + 1), dim)
+    eng.map_reset(1.0, float(R), dim)
+    ref = MapRef(dim, 1.0, float(R))
+    assert ref.R == R
+    rng = np.random.default_rng(18)
+    t = np.array([-5000.25, -77.5, -123456.75][:dim])
+    c = np.floor(t).astype(np.int64)
+    assert np.all(c < 0)
+    step = np.eye(dim, dtype=np.int64)
+
+    def scan(centre, seed_cells, n):
+        lo, hi = centre - R, centre + R
+        cells = [rng.integers(-R, R + 1, (n, dim)) + centre, lo[None], hi[None], lo + step, hi - step,
+                 lo - step, hi + step, np.tile(c + R // 3, (70, 1)), seed_cells]
+        cells = np.concatenate(cells)
+        return cells[rng.permutation(len(cells))]
+
+    def insert(cells, trans):
+        T = np.eye(dim + 1)
+        T[:dim, dim] = trans
+        pts = (cells.astype(np.float64) + 0.5) - trans          # the sensor-frame points: exact, and exact back
+        assert np.array_equal(pts + trans, cells + 0.5)
+        eng.map_insert(T, points=pts)
+        ref.insert(pts, T)
+        got = eng.map_get()
+        _check_against_ref(got, ref)
+        return got
+
+    first_cells = scan(c, np.zeros((0, dim), dtype=np.int64), 2000)
+    first = insert(first_cells, t)
+    assert np.array_equal(first[0][0], c - R) and np.array_equal(first[0][-1], c + R)
+    assert len(first[0]) == len(np.unique(first_cells, axis=0)) - 2 * dim and first[2].max() == 70
+    assert np.array_equal(first[1], first[0] + 0.5)
+    # the second insert: centred one cell further on every axis; 500 of the first scan's cells are hit again
+    second_cells = scan(c + 1, first_cells[:500], 1500)
+    second = insert(second_cells, t + 1.0)
+    seen = {tuple(r) for r in second[0].tolist()}
+    assert tuple(c - R) not in seen and tuple(c + R + 1) in seen          # forgotten; the new highest corner
+    assert np.array_equal(second[0][-1], c + 1 + R) and second[2].max() >= 140 and np.sum(second[2] == 2) >= 400
+    assert eng.map_size() == len(second[0]) == len(ref)
+
+
 # 5 ---------------------------------------------------------------------------------------------------------
 def _sequence(e, dim):
     rng = np.random.default_rng(14)

@@ -36,7 +36,28 @@ def _points(name, dim):
         return pts[rng.permutation(len(pts))], 1.0
     if name == "single_voxel":         # all 10,000 points in one voxel
         return rng.uniform(3.0, 3.25, (10000, dim)), 0.25
+    if name == "widest":               # the widest accepted key: 2^21 cells per axis in 3-D (63 bits), 2^31 in 2-D (62)
+        return _widest(dim)[0], 1.0
     raise KeyError(name)
+
+
+WIDEST_LOW = {3: (-1234567, -7, -2000001), 2: (-1234567891, -3)}     # lowest cells: negative, no powers of two
+
+
+def _widest(dim):
+    """(points, lowest cell per axis, highest cell per axis): about 3000 points at cell + 0.5 (leaf 1.0, exact in
+    fp64) whose cells span exactly 2^21 (3-D) or 2^31 (2-D) cells on every axis: both extreme corner cells (key
+    0 and the all-ones key), 70 points in one cell, a cell next to each corner, the rest scattered."""
+    rng = np.random.default_rng(17)
+    span = 2 ** 21 if dim == 3 else 2 ** 31
+    lo = np.array(WIDEST_LOW[dim], dtype=np.int64)
+    hi = lo + span - 1
+    cells = rng.integers(0, span, (2900, dim)) + lo
+    one = lo + span // 3
+    step = np.eye(dim, dtype=np.int64)
+    cells = np.concatenate([cells, lo[None], hi[None], lo + step, hi - step, np.tile(one, (70, 1))])
+    cells = cells[rng.permutation(len(cells))]
+    return cells.astype(np.float64) + 0.5, lo, hi
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,6 +117,32 @@ def test_voxels_that_span_waves(name, dim):
     assert case[3].max() >= 5000
     if name == "single_voxel":
         assert len(case[2]) == 1 and case[3][0] == 10000
+
+
+@pytest.mark.parametrize("dim", [3, 2])
+def test_widest_accepted_key(dim):
+    """Cells spanning exactly the limit on every axis (63 key bits in 3-D, 62 in 2-D), the lowest cell negative:
+    membership, order and counts exact against voxel_ref, centroids within the derived bound, the first and the
+    last row the two corner cells; one more point one cell beyond the range, on each axis and either side in
+    turn, is the first refused key."""
+    case = _case("widest", dim)
+    _check_exact(case)
+    _check_centroids(case)
+    pts, lo, hi = _widest(dim)
+    cells, cnt = case[6], case[3]
+    span = 2 ** 21 if dim == 3 else 2 ** 31
+    assert np.array_equal(cells.max(axis=0) - cells.min(axis=0) + 1, np.full(dim, span))
+    assert np.array_equal(cells[0], lo) and np.array_equal(cells[-1], hi) and np.all(lo < 0)
+    assert cnt.max() == 70 and len(cells) > 2900
+    assert np.array_equal(case[2], cells + 0.5)                 # every centroid is its cell's centre, exactly
+    for a in range(dim):
+        for edge, step in ((hi, 1), (lo, -1)):
+            beyond = edge.astype(np.float64) + 0.5
+            beyond[a] += step
+            with pytest.raises(ValueError, match=f"voxel grid too wide: axis {a}"):
+                gicp.voxel_downsample(np.concatenate([pts, beyond[None]]), 1.0)
+    again = gicp.voxel_downsample(pts, 1.0, return_counts=True)          # ... and a refusal changes nothing
+    assert np.array_equal(again[0], case[2]) and np.array_equal(again[1], cnt)
 
 
 def test_determinism_across_calls_and_engines():

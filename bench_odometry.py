@@ -47,6 +47,9 @@ def main():
                          "generated with NumPy); poses are compared at mid-sweep")
     ap.add_argument("--deskew", action="store_true",
                     help="de-skew every scan on the device as part of its build (Odometry(deskew=True); needs --skew)")
+    ap.add_argument("--report", action="store_true",
+                    help="evaluate every registration on the device (Odometry(report=...)): thresholds d_c / 4, d_c / 2, "
+                         "d_c and the quantiles 0.5 and 0.9")
     a = ap.parse_args()
     if a.deskew and not a.skew:
         ap.error("--deskew needs --skew (the plain stream carries no stamps)")
@@ -70,6 +73,7 @@ def main():
         frames = list(S.lidar_stream(a.frames, a.beams, a.azimuths, xp=xp, device=dev))
     gen_s = time.perf_counter() - t0
     kw = dict(max_distance_correspondence=0.5, max_distance_nearest_neighbors=1.0)
+    dc = kw["max_distance_correspondence"]
     import gicp
     p = gicp.default_params(3, max_iterations=a.max_iterations, tolerance=a.tolerance,
                             fixed_iterations=1 if a.fixed else 0, **kw)
@@ -78,7 +82,8 @@ def main():
         # two launches); --kernel-times keeps the library default (every 8th launch timed)
         p.timing_stride = -1
     odo = Odometry(3, params=p, borrow=not a.copy, voxel_size=a.voxel_size, map_voxel_size=a.map_voxel,
-                   map_range=a.map_range, map_min_points=a.map_min_points, deskew=a.deskew)
+                   map_range=a.map_range, map_min_points=a.map_min_points, deskew=a.deskew,
+                   report=dict(thresholds=[dc / 4, dc / 2, dc], quantiles=[0.5, 0.9]) if a.report else None)
     # warm-up on the first two frames (library init, allocation), then restart the stream
     odo.step(frames[0][0])
     odo.step(frames[1][0], frames[2][0])
@@ -87,7 +92,8 @@ def main():
     t1 = time.perf_counter()
     scans = [f for f, _ in frames]
     stream = (odo.step(s) for s in scans) if a.sync else odo.run(scans)
-    Ts = [T for T, _ in stream]   # the timed stream (the accuracy is evaluated below)
+    results = list(stream)        # the timed stream (the accuracy is evaluated below)
+    Ts = [T for T, _ in results]
     final_pose = odo.pose         # inside the timed region: flushes the per-frame pose compositions
     wall = time.perf_counter() - t1
     errs = []
@@ -141,6 +147,16 @@ def main():
         line["skew"] = {"deskew": bool(a.deskew), "pose_reference_stamp": 0.5,
                         "pose_error_final": pos_err[-1], "pose_error_median": float(np.median(pos_err[1:])),
                         "pose_error_max": float(np.max(pos_err))}
+    if a.report:
+        reps = [r["report"] for _, r in results if r is not None]
+        line["report"] = {"ms_per_frame": odo.timing["report_s"] * 1e3 / max(1, a.frames - 1),
+                          "share_of_frame": odo.timing["report_s"] / wall,
+                          "thresholds": [dc / 4, dc / 2, dc],
+                          "fitness_median": np.median([r["fitness"] for r in reps], axis=0).tolist(),
+                          "inlier_rmse_median": np.median([r["inlier_rmse"] for r in reps], axis=0).tolist(),
+                          "dist_q50_median": float(np.median([r["dist_q"][0.5] for r in reps])),
+                          "dist_q90_median": float(np.median([r["dist_q"][0.9] for r in reps])),
+                          "eig_min_median": float(np.median([r["eig"][0] for r in reps]))}
     if a.voxel_size is not None:
         line["voxel"] = {"voxel_size": a.voxel_size, "points_last_frame": odo.eng.cloud_size("source" if a.map_voxel else "target")}
     if a.map_voxel is not None:

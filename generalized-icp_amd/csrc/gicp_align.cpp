@@ -272,8 +272,9 @@ void top_enqueue(gicp_ctx* c, int k) {
     HIPCHK(hipMemcpyAsync(c->h_top + 32, ov, sizeof(double) * 16, hipMemcpyDeviceToHost, c->stream));
 }
 
-// One pass at pose T: statistics (all-reduced) into c->h_stats.
-void run_pass(gicp_ctx* c, const double* T, gicp_debug* dbg) {
+// One pass at pose T: statistics (all-reduced) into c->h_stats.  keep_on_device: the pass writes index, weight
+// and distance of every row into d_dbg_idx / d_dbg_w / d_dbg_dist and none is copied out (gicp_evaluate).
+void run_pass(gicp_ctx* c, const double* T, gicp_debug* dbg, bool keep_on_device) {
     require_clouds(c);
     const int d = c->src.dim;
     for (int k = 0; k < (d + 1) * (d + 1); ++k)
@@ -283,12 +284,12 @@ void run_pass(gicp_ctx* c, const double* T, gicp_debug* dbg) {
     upload_state(c, T, nullptr);
     CorrArgs a = corr_args(c, 1);
     c->top_ready = false;
-    if (dbg && (dbg->index || dbg->weight || dbg->distance || dbg->want_top_weights)) {
+    if (keep_on_device || (dbg && (dbg->index || dbg->weight || dbg->distance || dbg->want_top_weights))) {
         ensure_dbg(c);
-        a.dbg_index = dbg->index ? c->d_dbg_idx : nullptr;
-        a.dbg_weight = dbg->weight ? c->d_dbg_w : nullptr;
-        a.dbg_dist = dbg->distance ? c->d_dbg_dist : nullptr;
-        if (dbg->want_top_weights) {
+        a.dbg_index = keep_on_device || dbg->index ? c->d_dbg_idx : nullptr;
+        a.dbg_weight = keep_on_device || dbg->weight ? c->d_dbg_w : nullptr;
+        a.dbg_dist = keep_on_device || dbg->distance ? c->d_dbg_dist : nullptr;
+        if (dbg && dbg->want_top_weights) {
             fill_other_shards_det(c);
             a.dbg_det = c->d_dbg_det;
             a.top_tgt = c->d_top_tgt;
@@ -330,6 +331,101 @@ void run_pass(gicp_ctx* c, const double* T, gicp_debug* dbg) {
 #endif
     record_pass_info(c, c->h_stats + nstat(d));
     c->top_ready = a.dbg_det != nullptr;
+}
+
+// The report of one pass at pose T: run_pass with its per-point outputs kept on the device, the
+// overlap table and the quantiles reduced there (gicp_eval.hip), H, b and the spectra on the host from the pass's
+// statistics.  p's d_c, cov_model and robust kernel hold for this pass alone.
+void evaluate(gicp_ctx* c, const double* T, const gicp_params* p, const gicp_report_spec* spec, gicp_report* out) {
+    require_clouds(c);
+    if (c->nshards > 1) throw Fail{GICP_E_STATE, "gicp_evaluate needs an unsharded source (nshards == 1)"};
+    if (c->comm || c->hook || c->peer.n > 1)
+        throw Fail{GICP_E_STATE, "gicp_evaluate needs a context without a communicator, host hook or peer exchange"};
+    if (!out) throw Fail{GICP_E_INVALID, "out must not be NULL"};
+    const int d = c->src.dim, n1 = d + 1;
+    // the values in force come back whatever happens below
+    struct Restore {
+        gicp_params& live;
+        const gicp_params saved;
+        ~Restore() {
+            live.max_distance_correspondence = saved.max_distance_correspondence;
+            live.cov_model = saved.cov_model;
+            live.robust_kernel = saved.robust_kernel;
+            live.robust_scale = saved.robust_scale;
+        }
+    } restore{c->psrc, c->psrc};
+    const gicp_params prm = p ? resolve(d, p) : c->psrc;
+    check_report_spec(spec, prm.max_distance_correspondence);
+    double Tid[16];
+    for (int k = 0; k < n1 * n1; ++k) Tid[k] = T ? T[k] : ((k % (n1 + 1)) == 0 ? 1.0 : 0.0);
+    c->psrc.max_distance_correspondence = prm.max_distance_correspondence;
+    c->psrc.cov_model = prm.cov_model;
+    c->psrc.robust_kernel = prm.robust_kernel;
+    c->psrc.robust_scale = prm.robust_scale;
+    run_pass(c, Tid, nullptr, true);
+
+    gicp_report r;
+    std::memset(&r, 0, sizeof(r));
+    const double* st = c->h_stats;
+    r.dim = d;
+    r.n_thresholds = spec ? spec->n_thresholds : 0;
+    r.n_quantiles = spec ? spec->n_quantiles : 0;
+    r.n_source = c->src.n;
+    r.n_matched = (int64_t)st[nstat(d) - 1];
+    r.sum_sq = c->last_sq;
+    r.loss = st[nstat(d) - 2];
+    information(d, st, Tid, r.H, r.b);
+    report_spectra(&r);
+    for (int j = 0; j < GICP_REPORT_MAX; ++j) r.dist_q[j] = r.white_q[j] = std::nan("");
+    const int nq = r.n_matched > 0 ? r.n_quantiles : 0;   // no accepted row: every quantile stays NaN
+    if (r.n_thresholds > 0 || nq > 0) {
+        const size_t N = (size_t)c->src.n;
+        EvalArgs a{};
+        a.idx = c->d_dbg_idx;
+        a.dist = c->d_dbg_dist;
+        a.w = c->d_dbg_w;
+        a.src_xyz = c->src.xyz64;
+        a.src_inv = c->src.inv;
+        a.tgt_xyz = c->tgt.xyz64;
+        a.tgt_inv = c->tgt.inv;
+        a.n = c->src.n;
+        a.m = c->tgt.n;
+        a.dim = d;
+        a.nthr = r.n_thresholds;
+        a.nq = nq;
+        for (int i = 0; i < d; ++i) {
+            for (int k = 0; k < d; ++k) a.R[i * 3 + k] = Tid[i * n1 + k];
+            a.t[i] = Tid[i * n1 + d];
+        }
+        for (int j = 0; j < a.nthr; ++j) a.thr[j] = spec->thresholds[j];
+        for (int j = 0; j < nq; ++j)
+            a.rank[j] = a.rank[kEvalMax + j] = (unsigned long long)quantile_rank(spec->quantiles[j], r.n_matched);
+        if (nq > 0) c->d_eval_keys.reserve(2 * N);
+        c->d_eval_part.reserve((N + kEvalBlock - 1) / kEvalBlock * kEvalMax);
+        if (!c->d_eval_sel) c->d_eval_sel.alloc(1);
+        if (!c->d_eval_hist) c->d_eval_hist.alloc((size_t)kSelQueries * kSelBins);
+        if (!c->d_eval_out) c->d_eval_out.alloc(kEvalOutWords);
+        if (!c->h_eval_out) c->h_eval_out.alloc(kEvalOutWords);
+        a.keys = c->d_eval_keys;
+        a.part = c->d_eval_part;
+        a.sel = c->d_eval_sel;
+        a.hist = c->d_eval_hist;
+        a.out = c->d_eval_out;
+        HIPCHK(launch_eval(a, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_eval_out, c->d_eval_out, sizeof(unsigned long long) * kEvalOutWords, hipMemcpyDeviceToHost,
+                              c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const unsigned long long* w = c->h_eval_out;
+        for (int j = 0; j < a.nthr; ++j) {
+            r.inliers[j] = (int64_t)w[kEvalOutCnt + j];
+            std::memcpy(&r.inlier_sum_sq[j], &w[kEvalOutSum + j], sizeof(double));
+        }
+        for (int j = 0; j < nq; ++j) {
+            std::memcpy(&r.dist_q[j], &w[kEvalOutKey + j], sizeof(double));
+            std::memcpy(&r.white_q[j], &w[kEvalOutKey + kEvalMax + j], sizeof(double));
+        }
+    }
+    *out = r;
 }
 
 void align_trace(gicp_ctx* c, const double* T0, const gicp_params* p, double* T_out, gicp_result* res, gicp_trace* trace) {

@@ -82,7 +82,7 @@ void check_sweep_args(const double* xyz, const double* stamps, int64_t N, int di
 
 extern "C" {
 
-int gicp_version(void) { return 102; }
+int gicp_version(void) { return 103; }
 
 int gicp_stats_size(int dim) { return (dim == 2 || dim == 3) ? nstat(dim == 2 ? 2 : 3) : GICP_E_INVALID; }
 
@@ -330,6 +330,21 @@ int gicp_solve_pose(int dim, const double* stats, const double* T_k, double* T_o
     } catch (...) {
         return GICP_E_INVALID;
     }
+}
+
+// ---- the registration report ----
+
+int gicp_evaluate(gicp_ctx* c, const double* T, const gicp_params* p, const gicp_report_spec* spec, gicp_report* out) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_evaluate", [&] { evaluate(c, T, p, spec, out); });
+}
+
+int gicp_information(int dim, const double* stats, const double* T, double* H, double* b) {
+    return host_guard([&] { information(dim, stats, T, H, b); });
+}
+
+int gicp_sym_eig(int n, const double* A, double* w, double* V) {
+    return host_guard([&] { sym_eig(n, A, w, V); });
 }
 
 int gicp_align(gicp_ctx* c, const double* T0, const gicp_params* p, double* T_out, gicp_result* res) {

@@ -34,6 +34,7 @@ hipError_t voxel_temp_bytes(int64_t, int, size_t*, hipStream_t);
 hipError_t launch_voxel(const VoxelArgs&, hipStream_t);
 hipError_t launch_points_out(const double*, const int32_t*, int64_t, int, double*, hipStream_t);
 hipError_t launch_deskew(const SweepArgs&, hipStream_t);
+hipError_t launch_eval(const EvalArgs&, hipStream_t);
 hipError_t launch_map_insert(const VoxelArgs&, const MapArgs&, hipStream_t);
 hipError_t launch_map_centroids(const double*, int64_t, int, int, int32_t*, int32_t*, void*, size_t, double*,
                                 unsigned long long*, hipStream_t);
@@ -335,6 +336,14 @@ struct gicp_ctx {
     gicp::DevBuf<double*> d_peer_ptrs;      // device copy of the areas' addresses (PeerArgs::area)
     std::vector<float> iter_ms;       // sampled k_corr time per iteration of the last align (-1: not sampled)
     gicp::DevBuf<double> d_rot;       // gicp_rotated_covariances output
+    // gicp_evaluate: the two key arrays [2][N], the per-workgroup sums of the overlap table, the
+    // select's state and histograms, the result words and their pinned mirror
+    gicp::DevBuf<unsigned long long> d_eval_keys;
+    gicp::DevBuf<double> d_eval_part;
+    gicp::DevBuf<gicp::SelState> d_eval_sel;
+    gicp::DevBuf<uint32_t> d_eval_hist;
+    gicp::DevBuf<unsigned long long> d_eval_out;
+    gicp::PinnedBuf<unsigned long long> h_eval_out;
     // gicp_align_trace: per-iteration rows recorded on the device ([iter][(d+1)^2 + 1] pose + loss;
     // top-k rows [iter][16] source, target, det), copied out once after the loop
     gicp::DevBuf<double> d_hist;
@@ -371,11 +380,12 @@ void stage_target(gicp_ctx* c, const double* xyz, int64_t M, int dim, const gicp
 void commit_target(gicp_ctx* c, int shard, int nshards);
 void cancel_stage(gicp_ctx* c);
 
-// gicp_align.cpp: the per-source-tile state, one pass, the batched loop
+// gicp_align.cpp: the per-source-tile state, one pass, the batched loop, the report of a pass
 void reset_tile_state(gicp_ctx* c);
 void set_shard(gicp_ctx* c, int shard, int nshards);
 void top_enqueue(gicp_ctx* c, int k);
-void run_pass(gicp_ctx* c, const double* T, gicp_debug* dbg);
+void run_pass(gicp_ctx* c, const double* T, gicp_debug* dbg, bool keep_on_device = false);
+void evaluate(gicp_ctx* c, const double* T, const gicp_params* p, const gicp_report_spec* spec, gicp_report* out);
 void align_trace(gicp_ctx* c, const double* T0, const gicp_params* p, double* T_out, gicp_result* res, gicp_trace* trace);
 
 // gicp_exchange.cpp: the three statistics exchanges (RCCL, host hook, IPC peers); one per context

@@ -420,6 +420,167 @@ void check_shard(int shard, int nshards) {
 }
 
 // The exception in flight (call inside a catch block) as a GICP_E_* code and its text; the callers add their prefix.
+// ---- registration report ----
+
+// H = G^T H_z G and b = -G^T g of the pass's statistics `st` (layout DESIGN.md §4) at pose T, for the left
+// perturbation T' = Exp(xi) T: dz = G xi with z = (vec R row-major, t), dR = [w]x R, dt = w x t + v (2-D:
+// dR = w J2 R, dt = w J2 t + v).  H [n][n] row-major, b [n], n = 6 (3-D) or 3 (2-D).
+void information(int dim, const double* st, const double* T, double* H, double* b) {
+    if (dim != 2 && dim != 3) throw Fail{GICP_E_INVALID, "dim must be 2 or 3"};
+    if (!st || !T || !H || !b) throw Fail{GICP_E_INVALID, "stats, T, H and b must not be NULL"};
+    const int d = dim, n1 = d + 1, ns = d * (d + 1) / 2, nz = d * d + d, n = d == 3 ? 6 : 3, nw = n - d;
+    for (int k = 0; k < n1 * n1; ++k)
+        if (!std::isfinite(T[k])) throw Fail{GICP_E_INVALID, "pose contains non-finite values"};
+    const auto sym = [d](int a, int c) {
+        if (a > c) std::swap(a, c);
+        return a * d - a * (a - 1) / 2 + (c - a);
+    };
+    const double* A = st;
+    const double* B = A + ns * ns;
+    const double* C = B + ns * d;
+    const double* g = C + ns;   // gR [d][d], then gt [d]: g in z's order
+    double Hz[12][12];
+    for (int a = 0; a < d; ++a)
+        for (int i = 0; i < d; ++i) {
+            for (int c = 0; c < d; ++c) {
+                for (int j = 0; j < d; ++j) Hz[a * d + i][c * d + j] = A[sym(a, c) * ns + sym(i, j)];
+                Hz[a * d + i][d * d + c] = Hz[d * d + c][a * d + i] = B[sym(a, c) * d + i];
+            }
+        }
+    for (int a = 0; a < d; ++a)
+        for (int c = 0; c < d; ++c) Hz[d * d + a][d * d + c] = C[sym(a, c)];
+    // G [nz][n]: E[k][a][c] = ([e_k]x)_ac, the generator of axis k (2-D: the one generator J2)
+    double G[12][6] = {};
+    for (int k = 0; k < nw; ++k) {
+        double E[3][3] = {};
+        if (d == 2) {
+            E[0][1] = -1.0;
+            E[1][0] = 1.0;
+        } else {
+            const int u = (k + 1) % 3, v = (k + 2) % 3;   // e_k x e_u = e_v
+            E[v][u] = 1.0;
+            E[u][v] = -1.0;
+        }
+        for (int a = 0; a < d; ++a) {
+            for (int i = 0; i < d; ++i) {
+                double s = 0.0;
+                for (int c = 0; c < d; ++c) s += E[a][c] * T[c * n1 + i];
+                G[a * d + i][k] = s;
+            }
+            double s = 0.0;
+            for (int c = 0; c < d; ++c) s += E[a][c] * T[c * n1 + d];
+            G[d * d + a][k] = s;
+        }
+    }
+    for (int a = 0; a < d; ++a) G[d * d + a][nw + a] = 1.0;
+    double HG[12][6];
+    for (int i = 0; i < nz; ++i)
+        for (int k = 0; k < n; ++k) {
+            double s = 0.0;
+            for (int j = 0; j < nz; ++j) s += Hz[i][j] * G[j][k];
+            HG[i][k] = s;
+        }
+    for (int k = 0; k < n; ++k) {
+        for (int l = 0; l < n; ++l) {
+            double s = 0.0;
+            for (int i = 0; i < nz; ++i) s += G[i][k] * HG[i][l];
+            H[k * n + l] = s;
+        }
+        double s = 0.0;
+        for (int i = 0; i < nz; ++i) s += G[i][k] * g[i];
+        b[k] = -s;
+    }
+}
+
+// Eigenvalues (ascending) and unit eigenvectors (the columns of V, [n][n] row-major) of the symmetric part of A
+// ([n][n] row-major, n <= 6): cyclic Jacobi in fp64.  Each rotation annihilates one off-diagonal pair with the
+// stable tangent formula; the sweeps stop when every off-diagonal entry is exactly 0 or so small that its
+// rotation no longer changes the diagonal (relative 2^-53), which for these orders takes under ten sweeps.
+void sym_eig(int n, const double* A, double* w, double* V) {
+    if (n < 1 || n > 6) throw Fail{GICP_E_INVALID, "n must be 1..6"};
+    if (!A || !w || !V) throw Fail{GICP_E_INVALID, "A, w and V must not be NULL"};
+    double a[6][6], v[6][6];
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            if (!std::isfinite(A[i * n + j])) throw Fail{GICP_E_INVALID, "matrix contains non-finite values"};
+            a[i][j] = 0.5 * A[i * n + j] + 0.5 * A[j * n + i];
+            v[i][j] = i == j ? 1.0 : 0.0;
+        }
+    for (int sweep = 0; sweep < 64; ++sweep) {
+        bool rotated = false;
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = a[p][q];
+                if (apq == 0.0) continue;
+                const double app = a[p][p], aqq = a[q][q];
+                // negligible: |a_pq| below half an ulp of both diagonal entries
+                if (std::fabs(apq) <= 0x1p-54 * std::min(std::fabs(app), std::fabs(aqq))) {
+                    a[p][q] = a[q][p] = 0.0;
+                    continue;
+                }
+                rotated = true;
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                a[p][p] = app - t * apq;
+                a[q][q] = aqq + t * apq;
+                a[p][q] = a[q][p] = 0.0;
+                for (int k = 0; k < n; ++k) {
+                    if (k != p && k != q) {
+                        const double akp = a[k][p], akq = a[k][q];
+                        a[k][p] = a[p][k] = c * akp - s * akq;
+                        a[k][q] = a[q][k] = s * akp + c * akq;
+                    }
+                    const double vkp = v[k][p], vkq = v[k][q];
+                    v[k][p] = c * vkp - s * vkq;
+                    v[k][q] = s * vkp + c * vkq;
+                }
+            }
+        if (!rotated) break;
+    }
+    int order[6];
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order, order + n, [&](int x, int y) { return a[x][x] < a[y][y]; });
+    for (int k = 0; k < n; ++k) {
+        w[k] = a[order[k]][order[k]];
+        for (int i = 0; i < n; ++i) V[i * n + k] = v[i][order[k]];
+    }
+}
+
+// The degeneracy part of a report from its H: the spectra of H, its rotation block and its translation block.
+void report_spectra(gicp_report* r) {
+    const int d = r->dim, n = d == 3 ? 6 : 3, nw = n - d;
+    sym_eig(n, r->H, r->eig, r->eigvec);
+    double blk[9];
+    for (int i = 0; i < nw; ++i)
+        for (int j = 0; j < nw; ++j) blk[i * nw + j] = r->H[i * n + j];
+    sym_eig(nw, blk, r->eig_rot, r->vec_rot);
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) blk[i * d + j] = r->H[(nw + i) * n + nw + j];
+    sym_eig(d, blk, r->eig_trans, r->vec_trans);
+}
+
+// The rank of the lower order statistic of probability pi among n values: floor(pi (n - 1)), the product in fp64
+int64_t quantile_rank(double pi, int64_t n) {
+    const int64_t k = (int64_t)std::floor(pi * (double)(n - 1));
+    return std::max<int64_t>(0, std::min(n - 1, k));
+}
+
+// what gicp_evaluate refuses of a spec (NULL: nothing asked) under the pass's d_c
+void check_report_spec(const gicp_report_spec* s, double dc) {
+    if (!s) return;
+    if (s->n_thresholds < 0 || s->n_thresholds > GICP_REPORT_MAX)
+        throw Fail{GICP_E_INVALID, "n_thresholds must be 0..GICP_REPORT_MAX"};
+    if (s->n_quantiles < 0 || s->n_quantiles > GICP_REPORT_MAX)
+        throw Fail{GICP_E_INVALID, "n_quantiles must be 0..GICP_REPORT_MAX"};
+    for (int j = 0; j < s->n_thresholds; ++j)
+        if (!(std::isfinite(s->thresholds[j]) && s->thresholds[j] >= 0.0 && s->thresholds[j] <= dc))
+            throw Fail{GICP_E_INVALID, "a threshold must be finite and in [0, max_distance_correspondence] of the pass"};
+    for (int j = 0; j < s->n_quantiles; ++j)
+        if (!(s->quantiles[j] >= 0.0 && s->quantiles[j] <= 1.0))
+            throw Fail{GICP_E_INVALID, "a quantile probability must be in [0, 1]"};
+}
+
 int current_failure(std::string& msg) {
     try {
         throw;

@@ -1,5 +1,6 @@
 // gicp_hostmath.h — the part of the host layer that makes no HIP call (gicp_hostmath.cpp): the tiling and its
-// thread pool, the host scans, parameter defaults, the screen margins, the twist logarithm, the argument checks.
+// thread pool, the host scans, parameter defaults, the screen margins, the twist logarithm, the report's information
+// matrix and eigensolver, the argument checks.
 // Builds with the host compiler alone and links without the runtime (tests/native/host_check.cpp).
 #pragma once
 
@@ -107,6 +108,13 @@ int64_t map_window_lo(int axis, double t, double leaf, int64_t R);
 
 void motion_twist(int dim, const double* M, double* xi);
 void deskew_host(const double* xyz, const double* stamps, int64_t n, int dim, const double* xi, double ref, double* out);
+
+// registration report: information matrix of a pass's statistics, symmetric eigensolver
+void information(int dim, const double* stats, const double* T, double* H, double* b);
+void sym_eig(int n, const double* A, double* w, double* V);
+void report_spectra(gicp_report* r);
+int64_t quantile_rank(double pi, int64_t n);
+void check_report_spec(const gicp_report_spec* spec, double dc);
 
 void check_cloud_args(const double* xyz, int64_t n, int dim);
 void check_shard(int shard, int nshards);

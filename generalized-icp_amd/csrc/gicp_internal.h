@@ -357,6 +357,44 @@ struct MapArgs {
     double* sums_new;         // [m_old + n][4] out (the row after the last valid one takes the dropped rows' sum)
 };
 
+// Registration report (gicp_eval.hip): from the per-point outputs a pass left on the device
+// (index, distance, weight: original source order) the overlap table and two arrays of 64-bit keys -- the bit
+// patterns of dist_i and of the whitened residual s_i, all ones for a rejected row -- then an exact radix select of
+// up to kEvalMax ranks per key array, kSelBits bits per round from the top.  All pointers device memory.
+constexpr int kEvalMax = GICP_REPORT_MAX;
+constexpr int kEvalBlock = 256;                 // rows per workgroup of k_eval_values
+constexpr int kSelBits = 8;                     // digit width of the select: 8 rounds over a 64-bit key
+constexpr int kSelBins = 1 << kSelBits;
+constexpr int kSelRounds = 64 / kSelBits;
+constexpr int kSelQueries = 2 * kEvalMax;       // query q: key array q / kEvalMax, rank slot q % kEvalMax
+// result words (8 bytes each): inlier counts, their sums of dist^2 (fp64), the selected keys of both arrays
+constexpr int kEvalOutCnt = 0, kEvalOutSum = kEvalMax, kEvalOutKey = 2 * kEvalMax, kEvalOutWords = 4 * kEvalMax;
+struct SelState {
+    unsigned long long prefix[kSelQueries];     // the key bits found so far (the rounds' digits, top first)
+    unsigned long long rank[kSelQueries];       // the rank wanted among the keys that carry that prefix
+    int32_t slot[kSelQueries];                  // the first query of the same array with the same prefix: its histogram serves
+};
+struct EvalArgs {
+    const int64_t* idx;       // [n] matched target row, -1 rejected (CorrArgs::dbg_index)
+    const double* dist;       // [n] (CorrArgs::dbg_dist)
+    const double* w;          // [n][dim][dim] (CorrArgs::dbg_weight)
+    const double* src_xyz;    // the clouds' sorted fp64 points (DevCloud::xyz64, 4 doubles a row) ...
+    const int32_t* src_inv;   // ... and original -> sorted row
+    const double* tgt_xyz;
+    const int32_t* tgt_inv;
+    int64_t n, m;             // source and target rows
+    int32_t dim;
+    int32_t nthr, nq;         // thresholds; ranks per key array (0: no keys are written, no select runs)
+    double R[9], t[3];        // the pass's pose (R[a * 3 + b]; 2-D uses a, b < 2)
+    double thr[kEvalMax];
+    unsigned long long rank[kSelQueries];
+    unsigned long long* keys; // [2][n]
+    double* part;             // [ceil(n / kEvalBlock)][kEvalMax] per-workgroup sums of dist^2
+    SelState* sel;
+    uint32_t* hist;           // [kSelQueries][kSelBins]
+    unsigned long long* out;  // [kEvalOutWords]
+};
+
 constexpr int nstat(int D) {
     return (D * (D + 1) / 2) * (D * (D + 1) / 2) + (D * (D + 1) / 2) * D + (D * (D + 1) / 2) + D * D + D + 2;
 }

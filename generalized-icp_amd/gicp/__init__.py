@@ -19,10 +19,11 @@ from collections.abc import Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import Debug, Params, Result, Trace, check, dptr
+from ._lib import Debug, Params, Report, ReportSpec, Result, Trace, check, dptr
 
 __all__ = ["gicp", "apply_transformation", "Engine", "RotatedCovariances", "expand_stats", "stats_size",
-           "default_params", "last_result", "voxel_downsample", "deskew", "deskew_host", "motion_twist"]
+           "default_params", "last_result", "voxel_downsample", "deskew", "deskew_host", "motion_twist", "information",
+           "sym_eig"]
 
 
 def stats_size(dim):
@@ -477,6 +478,21 @@ class Engine:
               "gicp_iterate")
         return (st, out) if debug else st
 
+    def evaluate(self, T=None, params=None, thresholds=(), quantiles=()):
+        """One pass at pose T (None: identity) and its report (gicp_evaluate), reduced on the
+        device: a dict with the information matrix 'H' (6 x 6; 2-D 3 x 3, twist (omega, v), left perturbation)
+        and 'b', the spectra 'eig'/'eigvec' of H, 'eig_rot'/'vec_rot' and 'eig_trans'/'vec_trans' of its blocks
+        (ascending, eigenvectors in columns), per threshold 'inliers', 'inlier_sum_sq', 'fitness' and
+        'inlier_rmse', the lower order statistics 'dist_q' and 'white_q' keyed by probability, and 'n_source',
+        'n_matched', 'sum_sq', 'loss'.  params (None: the values in force) gives d_c, cov_model and the robust
+        kernel of this pass alone."""
+        spec, thr, qs = _report_spec(thresholds, quantiles)
+        Tp = None if T is None else np.ascontiguousarray(np.asarray(T, dtype=np.float64))
+        rep = Report()
+        check(self._lib.gicp_evaluate(self._ctx, None if Tp is None else dptr(Tp), C.byref(params) if params else None,
+                                      C.byref(spec), C.byref(rep)), self._ctx, "gicp_evaluate")
+        return _report_dict(rep, thr, qs)
+
     def pass_info(self):
         """Diagnostics of the last pass: walking lanes the fp32 screen left ambiguous (re-resolved in fp64),
         pairs screened, list rebuilds, sum |r|^2, lanes proved by the graph descent (its near ties, resolved
@@ -537,6 +553,72 @@ class Engine:
             for k in ("top_src", "top_tgt", "top_det"):
                 out.pop(k)
         return Tout, r, out
+
+
+def _report_spec(thresholds, quantiles):
+    """gicp_report_spec of the two sequences (their lengths are the library's to refuse)."""
+    thr = [float(v) for v in thresholds]
+    qs = [float(v) for v in quantiles]
+    spec = ReportSpec()
+    spec.n_thresholds, spec.n_quantiles = len(thr), len(qs)
+    for k, v in enumerate(thr[:_lib.REPORT_MAX]):
+        spec.thresholds[k] = v
+    for k, v in enumerate(qs[:_lib.REPORT_MAX]):
+        spec.quantiles[k] = v
+    return spec, thr, qs
+
+
+def _report_dict(rep, thr, qs):
+    """The gicp_report as a dict: arrays shaped n x n, the two ratios of the overlap table, quantiles keyed by
+    probability."""
+    d = int(rep.dim)
+    n, nw = (6, 3) if d == 3 else (3, 1)
+    nt, nq = int(rep.n_thresholds), int(rep.n_quantiles)
+    arr = lambda f, k: np.array(f[:k], dtype=np.float64)
+    inl = np.array(rep.inliers[:nt], dtype=np.int64)
+    ssq = arr(rep.inlier_sum_sq, nt)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        fitness = inl / float(rep.n_source) if rep.n_source else np.full(nt, np.nan)
+        rmse = np.where(inl > 0, np.sqrt(ssq / np.maximum(inl, 1)), np.nan)
+    return dict(
+        dim=d, n_source=int(rep.n_source), n_matched=int(rep.n_matched), sum_sq=float(rep.sum_sq), loss=float(rep.loss),
+        H=arr(rep.H, n * n).reshape(n, n), b=arr(rep.b, n),
+        eig=arr(rep.eig, n), eigvec=arr(rep.eigvec, n * n).reshape(n, n),
+        eig_rot=arr(rep.eig_rot, nw), vec_rot=arr(rep.vec_rot, nw * nw).reshape(nw, nw),
+        eig_trans=arr(rep.eig_trans, d), vec_trans=arr(rep.vec_trans, d * d).reshape(d, d),
+        thresholds=np.array(thr[:nt]), inliers=inl, inlier_sum_sq=ssq, fitness=fitness, inlier_rmse=rmse,
+        quantiles=np.array(qs[:nq]),
+        dist_q={qs[k]: float(rep.dist_q[k]) for k in range(nq)},
+        white_q={qs[k]: float(rep.white_q[k]) for k in range(nq)})
+
+
+def information(stats, T):
+    """(H, b) of a pass's statistics at pose T for the left perturbation T' = Exp(xi) T, xi = (omega, v): the
+    Gauss-Newton Hessian sum J^T W J and sum J^T W r, J = [[p]x, -I] (gicp_information, host only).  H is 6 x 6
+    (2-D: 3 x 3)."""
+    T = np.ascontiguousarray(np.asarray(T, dtype=np.float64))
+    d = T.shape[0] - 1
+    st = np.ascontiguousarray(np.asarray(stats, dtype=np.float64))
+    if T.shape != (d + 1, d + 1) or d not in (2, 3) or st.shape != (stats_size(d),):
+        raise ValueError("information: T must be 3 x 3 or 4 x 4 and stats the statistics of that dimension")
+    n = 6 if d == 3 else 3
+    H = np.empty((n, n))
+    b = np.empty(n)
+    check(_lib.load().gicp_information(d, dptr(st), dptr(T), dptr(H), dptr(b)), None, "gicp_information")
+    return H, b
+
+
+def sym_eig(A):
+    """(w, V) of the symmetric part of A (order <= 6): eigenvalues ascending, V[:, k] the unit eigenvector of
+    w[k] (gicp_sym_eig: cyclic Jacobi in fp64, host only)."""
+    A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError("sym_eig: A must be square")
+    n = A.shape[0]
+    w = np.empty(n)
+    V = np.empty((n, n))
+    check(_lib.load().gicp_sym_eig(n, dptr(A), dptr(w), dptr(V)), None, "gicp_sym_eig")
+    return w, V
 
 
 def solve_pose(stats, T_k):

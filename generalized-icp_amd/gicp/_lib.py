@@ -118,6 +118,45 @@ class Sweep(C.Structure):
     ]
 
 
+REPORT_MAX = 8
+
+
+class ReportSpec(C.Structure):
+    """gicp_report_spec (include/gicp_hip.h): the thresholds and quantile probabilities of gicp_evaluate."""
+    _fields_ = [
+        ("n_thresholds", C.c_int32),
+        ("n_quantiles", C.c_int32),
+        ("thresholds", C.c_double * REPORT_MAX),
+        ("quantiles", C.c_double * REPORT_MAX),
+    ]
+
+
+class Report(C.Structure):
+    """gicp_report (include/gicp_hip.h): what gicp_evaluate returns."""
+    _fields_ = [
+        ("dim", C.c_int32),
+        ("n_thresholds", C.c_int32),
+        ("n_quantiles", C.c_int32),
+        ("pad", C.c_int32),
+        ("n_source", C.c_int64),
+        ("n_matched", C.c_int64),
+        ("sum_sq", C.c_double),
+        ("loss", C.c_double),
+        ("H", C.c_double * 36),
+        ("b", C.c_double * 6),
+        ("eig", C.c_double * 6),
+        ("eigvec", C.c_double * 36),
+        ("eig_rot", C.c_double * 3),
+        ("vec_rot", C.c_double * 9),
+        ("eig_trans", C.c_double * 3),
+        ("vec_trans", C.c_double * 9),
+        ("inliers", C.c_int64 * REPORT_MAX),
+        ("inlier_sum_sq", C.c_double * REPORT_MAX),
+        ("dist_q", C.c_double * REPORT_MAX),
+        ("white_q", C.c_double * REPORT_MAX),
+    ]
+
+
 # every entry point include/gicp_hip.h declares: name -> (restype, argtypes)
 _VP = C.c_void_p
 _DP = C.POINTER(C.c_double)
@@ -176,6 +215,9 @@ SIGNATURES = {
     "gicp_map_size": (C.c_int, [_VP, C.POINTER(C.c_int64)]),
     "gicp_map_get": (C.c_int, [_VP, C.POINTER(C.c_int32), _DP, C.POINTER(C.c_int32)]),
     "gicp_map_to_target": (C.c_int, [_VP, C.POINTER(Params), C.c_int]),
+    "gicp_evaluate": (C.c_int, [_VP, _DP, C.POINTER(Params), C.POINTER(ReportSpec), C.POINTER(Report)]),
+    "gicp_information": (C.c_int, [C.c_int, _DP, _DP, _DP, _DP]),
+    "gicp_sym_eig": (C.c_int, [C.c_int, _DP, _DP, _DP]),
 }
 
 # gicp_allreduce_fn: int (*)(double* buf, int n, void* user)
@@ -186,7 +228,7 @@ _lib = None
 # the sources gicp_build_info()'s hash covers, in the Makefile's HASH_SRCS order
 HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
              "csrc/gicp_build.cpp", "csrc/gicp_align.cpp", "csrc/gicp_exchange.cpp", "csrc/gicp_voxel.hip",
-             "csrc/gicp_sweep.hip", "csrc/gicp_internal.h", "csrc/gicp_mem.h", "csrc/gicp_sweep.h",
+             "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_internal.h", "csrc/gicp_mem.h", "csrc/gicp_sweep.h",
              "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
              "../include/gicp_hip.h")
 

@@ -24,6 +24,9 @@ Motion compensation (`deskew=True`): a scan is then N x (dim+1),
 stamps in units of one sweep ([0, 1) over the sweep), and every scan is de-skewed on the device, as part of its
 build, to the stamp `deskew_ref` (0.5: mid-sweep, so the poses are the sensor's at mid-sweep) under the
 constant-velocity prediction of the sensor's motion over one sweep.
+
+Registration report (`report=dict(thresholds=..., quantiles=...)`): every registration is followed by
+one `Engine.evaluate` at the pose it found, against the target it used, and the report is the result's "report".
 """
 import math
 import time
@@ -36,7 +39,7 @@ from . import Engine, default_params
 class Odometry:
     def __init__(self, dim=3, params=None, device=0, composition="se3", init="constant_velocity", borrow=False,
                  voxel_size=None, voxel_min_points=1, map_voxel_size=None, map_range=None, map_min_points=1,
-                 deskew=False, deskew_ref=0.5, **kw):
+                 deskew=False, deskew_ref=0.5, report=None, **kw):
         if composition not in ("se3", "reference"):
             raise ValueError("composition must be 'se3' or 'reference'")
         if init not in ("identity", "constant_velocity"):
@@ -72,6 +75,14 @@ class Odometry:
         # deskew_ref by the predicted motion over one stamp unit (_predicted_motion)
         self.deskew = bool(deskew)
         self.deskew_ref = float(deskew_ref)
+        # report: None, or the keywords of Engine.evaluate (thresholds=, quantiles=) -- each registration is then
+        # evaluated at its final pose against the target it used (scan-to-map: before the scan is merged and the
+        # map rebuilt) and the report goes into the result dict under "report".  It reads the registration; it
+        # steers nothing
+        if report is not None and set(report) - {"thresholds", "quantiles"}:
+            raise ValueError("report takes the keys 'thresholds' and 'quantiles'")
+        self.report = None if report is None else dict(thresholds=tuple(report.get("thresholds", ())),
+                                                       quantiles=tuple(report.get("quantiles", ())))
         self.reset()
 
     def reset(self):
@@ -87,6 +98,8 @@ class Odometry:
             self.eng.cancel_stage()
         self._staged = []                    # the scan objects whose builds are staged, oldest first
         self.timing = {"setup_s": 0.0, "align_s": 0.0, "iterations": 0}
+        if getattr(self, "report", None) is not None:
+            self.timing["report_s"] = 0.0
         if getattr(self, "map_voxel_size", None) is not None:
             self.eng.map_reset(self.map_voxel_size, self.map_range, dim)
             self.timing.update(map_s=0.0, map_insert_s=0.0, map_target_s=0.0)
@@ -113,6 +126,14 @@ class Odometry:
         if a.ndim != 2 or a.shape[1] != self.dim + 1:
             raise ValueError(f"with deskew=True a scan is N x {self.dim + 1} (points, then the stamp), got shape {a.shape}")
         return {"stamps": np.ascontiguousarray(a[:, self.dim]), "motion": self._predicted_motion(), "ref": self.deskew_ref}
+
+    def _evaluate(self, T, res):
+        """The report of the registration that ended at pose T, into res (nothing with report=None)."""
+        if getattr(self, "report", None) is None:
+            return
+        t = time.perf_counter()
+        res["report"] = self.eng.evaluate(T, None, **self.report)   # (params None: those the align left in force)
+        self.timing["report_s"] += time.perf_counter() - t
 
     def step(self, scan, next_scan=None, next_scans=()):
         """Add one scan; returns (T, result) of its registration against the previous scan, or
@@ -165,6 +186,7 @@ class Odometry:
         T, res = self.eng.align(T0, self.params)
         self.timing["align_s"] += time.perf_counter() - t1
         self.timing["iterations"] += res["iterations"]
+        self._evaluate(T, res)
         self.last_T = T
         self._integrate(T)
         return T, res
@@ -188,6 +210,8 @@ class Odometry:
             t2 = time.perf_counter()
             self.timing["align_s"] += t2 - t1
             self.timing["iterations"] += res["iterations"]
+            self._evaluate(P, res)
+            t2 = time.perf_counter()
             T = np.linalg.inv(P) @ prev
             self.last_T = T
             self._pose = P

@@ -157,7 +157,9 @@ typedef struct gicp_debug {
 /* ---- library ------------------------------------------------------------ */
 int gicp_version(void);                          /* 100 * major + minor; 101: gicp_params grew by robust_kernel,
                                                     pad_robust, robust_scale (appended); 102: motion
-                                                    compensation (gicp_sweep, gicp_deskew, gicp_*_sweep) */
+                                                    compensation (gicp_sweep, gicp_deskew, gicp_*_sweep); 103: the
+                                                    registration report (gicp_evaluate, gicp_information,
+                                                    gicp_sym_eig) */
 int gicp_stats_size(int dim);                    /* 26 (dim 2) or 74 (dim 3) */
 void gicp_default_params(int dim, gicp_params* out);
 const char* gicp_strerror(int code);
@@ -202,8 +204,9 @@ int gicp_peer_close(gicp_ctx* ctx);   /* back to no exchange (RCCL / hook as set
 
 /* Build provenance of this library: "src=<first 16 hex of sha256 over the sources>;git=<rev>;built=<date
  * time>;arch=gfx950".  The source hash covers csrc/{gicp_kernels.hip, gicp_capi.cpp, gicp_solver.cpp,
- * gicp_cg.cpp, gicp_voxel.hip, gicp_sweep.hip, gicp_internal.h, gicp_mem.h, gicp_sweep.h, gicp_solver.h, gicp_solve_dev.h} and
- * include/gicp_hip.h, concatenated in that order, so
+ * gicp_cg.cpp, gicp_hostmath.cpp, gicp_build.cpp, gicp_align.cpp, gicp_exchange.cpp, gicp_voxel.hip, gicp_sweep.hip,
+ * gicp_eval.hip, gicp_internal.h, gicp_mem.h, gicp_sweep.h, gicp_solver.h, gicp_solve_dev.h, gicp_hostmath.h,
+ * gicp_host.h} and include/gicp_hip.h, concatenated in that order, so
  * a caller can prove the loaded library was compiled from the sources beside it. */
 const char* gicp_build_info(void);
 
@@ -478,6 +481,78 @@ int gicp_map_insert_points(gicp_ctx* ctx, const double* xyz, int64_t n, int dim,
 int gicp_map_size(gicp_ctx* ctx, int64_t* rows);                /* 0 before gicp_map_reset */
 int gicp_map_get(gicp_ctx* ctx, int32_t* cells, double* centroids, int32_t* counts);
 int gicp_map_to_target(gicp_ctx* ctx, const gicp_params* p, int min_points);
+
+/* ---- registration report -------------------------------------------------------------
+ * One pass at pose T and, from it, what a consumer needs to judge the registration; no per-point array
+ * reaches the host.  The pass accepts a set of source points; for each accepted point i
+ *     p_i = R s_i + t,  q_i its match,  r_i = q_i - p_i,
+ *     W~_i the weight the pass used (cov_model and robust kernel in force: exactly gicp_debug.weight),
+ *     dist_i = gicp_debug.distance.
+ *
+ * Information matrix.  Left perturbation T' = Exp(xi) T, twist layout as gicp_sweep: 3-D
+ * (w_x, w_y, w_z, v_x, v_y, v_z), 2-D (w, v_x, v_y).  J_i = d r_i / d xi = [ [p_i]x , -I ] (2-D:
+ * [ -J2 p_i , -I ], J2 = [[0,-1],[1,0]]), H = sum J_i^T W~_i J_i, b = sum J_i^T W~_i r_i; the Gauss-Newton step
+ * is -H^-1 b and the frozen-weight loss is c0 + 2 b^T xi + xi^T H xi to second order.  Both follow from the pass's
+ * statistics with no per-point work: with H_z, g of DESIGN.md §4 and dz = G xi (dR = [w]x R, dt = w x t + v),
+ * H = G^T H_z G and b = -G^T g (gicp_information).  n = 6 (3-D) or 3 (2-D); H is n x n row-major.
+ *
+ * Degeneracy.  Eigenvalues ascending and eigenvectors (columns, n x n row-major) of three matrices: H (mixed
+ * units: radians and metres), its rotation block H_ww (3 x 3; 2-D: 1 x 1) and its translation block H_vv (dim x
+ * dim).  All three are defined for a singular H too (no Schur complement is taken).  gicp_sym_eig is a cyclic
+ * Jacobi iteration in fp64 on (A + A^T) / 2.
+ *
+ * Overlap table.  Up to GICP_REPORT_MAX thresholds tau_j, each finite with 0 <= tau_j <= d_c of the pass (the
+ * search is exact only up to d_c): inliers[j] = #{i accepted : dist_i <= tau_j} (inclusive, as d_c is) and
+ * inlier_sum_sq[j] = sum of dist_i^2 over them.  Fitness is inliers[j] / n_source, the inlier RMSE
+ * sqrt(inlier_sum_sq[j] / inliers[j]).  The sums are added in an order fixed by the cloud's size (no
+ * floating-point atomics): bit-identical from call to call and from context to context.
+ *
+ * Quantiles.  Up to GICP_REPORT_MAX probabilities pi_j in [0, 1]; the statistic is the lower order statistic:
+ * of the n accepted values sorted ascending the one at index floor(pi_j (n - 1)), the product in fp64
+ * (np.quantile(v, pi, method="lower")), exact, of two value sets: dist_q of the distances dist_i, white_q of the
+ * whitened residuals s_i = sqrt(max(r_i^T W~_i r_i, 0)) -- the unit of robust_scale when the pass runs with
+ * GICP_ROBUST_NONE.  With n = 0 every quantile is NaN, the counts are 0 and H, b and the eigenvalues are 0:
+ * not an error.
+ *
+ * gicp_evaluate: T = NULL is the identity; p = NULL means the values in force; otherwise p's
+ * max_distance_correspondence, cov_model, robust_kernel and robust_scale are used FOR THIS PASS ALONE and the
+ * values in force are restored afterwards (unlike gicp_align, whose values stay).  spec = NULL: no thresholds,
+ * no quantiles.  It counts as a pass (gicp_pass_info describes it) and uses and updates the pose-dependent
+ * caches as gicp_iterate does; they change no result.  One stream synchronisation more than gicp_iterate.
+ * GICP_E_STATE: clouds not set, a sharded source (nshards > 1), or a communicator, host hook or peer exchange
+ * set (quantiles do not sum over ranks).  GICP_E_INVALID: a non-finite T, a count < 0 or > GICP_REPORT_MAX, a
+ * threshold or probability out of range, out == NULL.
+ * gicp_information and gicp_sym_eig are host only, as gicp_solve_pose: no HIP call, no context.  gicp_evaluate
+ * calls exactly these two on the pass's statistics. */
+#define GICP_REPORT_MAX 8
+typedef struct gicp_report_spec {
+    int32_t n_thresholds, n_quantiles;
+    double thresholds[GICP_REPORT_MAX];
+    double quantiles[GICP_REPORT_MAX];
+} gicp_report_spec;
+typedef struct gicp_report {
+    int32_t dim;               /* 2 or 3; n = 3 or 6 below */
+    int32_t n_thresholds, n_quantiles;   /* as asked */
+    int32_t pad;
+    int64_t n_source;          /* rows of the source cloud */
+    int64_t n_matched;         /* accepted correspondences: the statistics' count */
+    double sum_sq;             /* sum |r_i|^2 (gicp_pass_info out[3]) */
+    double loss;               /* c0 = sum r_i^T W~_i r_i */
+    double H[36], b[6];        /* n x n row-major, n */
+    double eig[6], eigvec[36]; /* of H: ascending; eigvec[i * n + k] = component i of eigenvector k */
+    double eig_rot[3], vec_rot[9];       /* of H_ww (3 x 3; 2-D: 1 x 1) */
+    double eig_trans[3], vec_trans[9];   /* of H_vv (dim x dim) */
+    int64_t inliers[GICP_REPORT_MAX];
+    double inlier_sum_sq[GICP_REPORT_MAX];
+    double dist_q[GICP_REPORT_MAX], white_q[GICP_REPORT_MAX];
+} gicp_report;
+int gicp_evaluate(gicp_ctx* ctx, const double* T, const gicp_params* p, const gicp_report_spec* spec,
+                  gicp_report* out);
+/* H [n][n] and b [n] from `stats` (gicp_iterate's output at pose T, (dim+1)^2 row-major) */
+int gicp_information(int dim, const double* stats, const double* T, double* H, double* b);
+/* A [n][n] row-major, 1 <= n <= 6 (only (A + A^T) / 2 is used) -> w[n] ascending, V[n][n] with column k the
+ * unit eigenvector of w[k].  GICP_E_INVALID for n out of range, a NULL pointer or a non-finite entry. */
+int gicp_sym_eig(int n, const double* A, double* w_ascending, double* V_columns_row_major);
 
 #ifdef __cplusplus
 }

@@ -77,7 +77,8 @@ def test_pass_info_sum_sq_vs_oracle_mse(eng, scene3d):
 @pytest.mark.parametrize("dim", [2, 3])
 def test_top_weights_vs_argsort(eng, scene3d, dim):
     """gicp_top_weights == np.argsort(np.linalg.det(W))[-5:] of the same pass (gicp.py:170): the det
-    values to 1e-9 and, where they are distinct, the same source points in the same order."""
+    values to 1e-9 and, where they are distinct, the same source points in the same order.  (Equal dets, every
+    k, pads, shards and the sizes beyond 65 536 rows: test_gpu_topk.py, bit for bit against tests/topk_ref.py.)"""
     if dim == 3:
         src, tgt, _ = scene3d
         p = gicp.default_params(3, **P3)

@@ -1,8 +1,9 @@
 """GPU tests of the registration report (gicp_evaluate, include/gicp_hip.h "registration report"):
 H and b against the NumPy restatement tests/report_ref.py on the oracle's weights, the overlap table and the
 quantiles against the engine's own per-point arrays, the shapes at which the kernels of csrc/gicp_eval.hip can go
-wrong (a lone lane, a wave edge, a workgroup edge, several workgroups; every value equal; nothing accepted; ties
-across a rank), what the call leaves behind, a degenerate scene, the refusals, and Odometry(report=...)."""
+wrong (a lone lane, a wave edge, a workgroup edge, several workgroups, the 65 536 and 262 144 rows above which
+k_eval_sums and k_sel_hist take their second paths; every value equal; nothing accepted; ties across a rank, at
+257 rows and at 262 401), what the call leaves behind, a degenerate scene, the refusals, and Odometry(report=...)."""
 import numpy as np
 import pytest
 
@@ -184,14 +185,42 @@ def prefix_cloud():
     return src, tgt
 
 
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4097])
-def test_source_sizes(eng, prefix_cloud, n):
-    src, tgt = prefix_cloud
+@pytest.fixture(scope="module")
+def long_prefix_cloud():
+    """262 401 source rows = 1025 workgroups of k_eval_values and one row: above both thresholds of the report's
+    second code paths.  k_eval_sums gives each of its 256 threads a run of ceil(workgroups / 256)
+    partials, longer than one from 65 537 rows on; k_sel_hist has at most kSelGridMax = 1024 workgroups and takes
+    the keys beyond 262 144 by its grid stride."""
+    src, tgt, _ = S.scene_pair_3d(262401, 3000)
+    return src, tgt
+
+
+def _block_edge_probabilities(m):
+    """8 probabilities for m accepted rows: 0, 1, and six whose rank floor(pi (m - 1)) is the last row of a 256-row
+    block of the sorted values or the first row of the next (asserted): the first block's end, the middle's, the
+    last whole one's."""
+    assert m > 1024
+    ends = (255, 256 * (m // 512) - 1, 256 * ((m - 2) // 256) - 1)
+    ranks = [r for e in ends for r in (e, e + 1)]
+    qs = (0.0,) + tuple((r + 0.5) / (m - 1) for r in ranks) + (1.0,)
+    assert [int(np.floor(pi * (m - 1))) for pi in qs[1:-1]] == ranks and ranks[-1] < m - 1
+    assert sorted(set(ranks)) == ranks and all(r % 256 in (0, 255) for r in ranks)
+    return qs
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 4097, 65536, 65537, 262144, 262145, 262401])
+def test_source_sizes(eng, prefix_cloud, long_prefix_cloud, n):
+    src, tgt = prefix_cloud if n <= 4097 else long_prefix_cloud
     src = np.ascontiguousarray(src[:n])
     p = gicp.default_params(3, max_distance_correspondence=1.0, max_distance_nearest_neighbors=1.0)
     eng.set_target(tgt, p)
     eng.set_source(src, p)
-    rep, _, _ = check_against_debug(eng, src, tgt, _pose3(), (0.0, 0.25, 0.5, 1.0), QS, f"prefix {n}")
+    thr, qs = (0.0, 0.25, 0.5, 1.0), QS
+    if n > 4097:                                             # the full width of the spec: 8 thresholds, 8 probabilities
+        thr = (0.0, 0.05, 0.125, 0.25, 0.5, 0.75, 0.9, 1.0)
+        qs = _block_edge_probabilities(int(eng.iterate(_pose3())[-1]))
+        assert len(qs) == 8 and len(set(qs)) == 8
+    rep, _, _ = check_against_debug(eng, src, tgt, _pose3(), thr, qs, f"prefix {n}")
     if n >= 63:                                              # (these clouds are sparse: about a quarter is rejected)
         assert 0 < rep["n_matched"] < n
 
@@ -246,6 +275,41 @@ def test_ties_across_a_rank(eng):
     assert rep["dist_q"] == want and rep["white_q"] == want             # W = I: s = dist, exactly
     assert list(rep["inliers"]) == [128, 257]
     assert list(rep["inlier_sum_sq"]) == [128 * 0.0625, 128 * 0.0625 + 129 * 0.140625]
+
+
+def test_two_values_at_full_scale(eng):
+    """test_ties_across_a_rank at 262 401 rows (1025 workgroups and one row: k_eval_sums' runs of 5 partials,
+    k_sel_hist's grid stride) against a 65^3 lattice: every key of a class is the same 64 bits, so every round of
+    the select takes the one-add-per-wave branch with counts above 2^16 in a bin, and k_sel_narrow's prefix sum
+    runs over them.  131 201 rows at 0.25, 131 200 at 0.375: rank floor(0.5 (n - 1)) = 131 200 is the last 0.25.
+    Every partial sum of the squares is a multiple of 2^-6 below 2^53: exact in any order."""
+    g = np.stack(np.meshgrid(*(np.arange(65.0),) * 3, indexing="ij"), -1).reshape(-1, 3)
+    rng = np.random.default_rng(9)
+    tgt = g[rng.permutation(len(g))]
+    n, n1 = 262401, 131201
+    n2 = n - n1
+    src = tgt[rng.permutation(len(tgt))[:n]].copy()
+    off = np.where(rng.permutation(n) < n1, 0.25, 0.375)
+    src[:, 0] += off
+    assert int(np.floor(0.5 * (n - 1))) == n1 - 1 and np.sum(off == 0.25) == n1
+    p = gicp.default_params(3, max_distance_correspondence=0.5, max_distance_nearest_neighbors=1.5,
+                            cov_model=MODELS["point_to_point"])
+    eng.set_target(tgt, p)
+    eng.set_source(src, p)
+    below, above = np.nextafter(0.5, 0.0), np.nextafter(0.5, 1.0)
+    first = (n1 + 0.5) / (n - 1)                             # the first 0.375
+    qs = (0.0, below, 0.5, above, first, 1.0)
+    rep, _, dbg = check_against_debug(eng, src, tgt, np.eye(4), (0.25, 0.375), qs, "lattice ties, 262 401 rows")
+    assert np.array_equal(dbg["distance"], off)
+    assert rep["n_matched"] == n
+    want = {pi: 0.25 if int(np.floor(pi * (n - 1))) < n1 else 0.375 for pi in qs}     # the rank in fp64, as specified
+    assert want[0.5] == 0.25 and want[first] == 0.375 and int(np.floor(first * (n - 1))) == n1
+    assert rep["dist_q"] == want and rep["white_q"] == want             # W = I: s = dist, exactly
+    assert list(rep["inliers"]) == [n1, n]
+    assert list(rep["inlier_sum_sq"]) == [n1 * 0.0625, n1 * 0.0625 + n2 * 0.140625]
+    again = eng.evaluate(np.eye(4), thresholds=(0.25, 0.375), quantiles=qs)
+    assert np.array_equal(again["inlier_sum_sq"], rep["inlier_sum_sq"]) and np.array_equal(again["inliers"], rep["inliers"])
+    assert again["dist_q"] == rep["dist_q"] and again["white_q"] == rep["white_q"]
 
 
 # 5 --------------------------------------------------------------------------------------------------------

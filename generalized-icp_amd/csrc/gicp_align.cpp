@@ -235,7 +235,7 @@ void reset_tile_state(gicp_ctx* c) {
     // hints -1, lists empty, certificates none (cert_pass -1) and no last match (cert_j -1: k_corr's per-lane
     // search cap) -- one launch (five memsets were five queue operations, ~40 us of a C5 frame)
     HIPCHK(launch_reset_tiles(c->d_hint, c->d_list_len, c->d_list_rcert, c->d_cert_pass, nt, c->d_cert_j,
-                              c->d_cert_j ? std::max<int64_t>(1, c->src.n) : 0, c->stream));
+                              c->d_cert_j ? std::max<int64_t>(1, c->src.n) : 0, c->d_poses, c->stream));
     c->pass = 0;
 }
 

@@ -1,5 +1,5 @@
-// gicp_build.cpp — everything that makes a cloud on the device: the build and its front (upload, de-skew, voxel
-// filter), the copies out of a cloud, the local voxel map, and the ring of staged targets with its threads.
+// gicp_build.cpp — everything that makes a cloud on the device: the build and its front (upload, de-skew, input
+// filters, voxel filter), the copies out of a cloud, the local voxel map, and the ring of staged targets with its threads.
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "gicp_host.h"
@@ -86,6 +86,113 @@ VoxelOut voxel_filter(BuildScratch& bs, const double* d_raw, int64_t n, int dim,
     }
     decode_bounds(res, dim, vo.mn, vo.mx);
     return vo;
+}
+
+struct FilterOut {
+    double* pts = nullptr;          // the survivors [M][dim], rows in their order
+    const int32_t* idx = nullptr;   // the row of each in the input (tracked; null otherwise)
+    int64_t M = 0;
+    double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};   // their exact bounds
+};
+
+bool filter_on(const gicp_filter& f) { return filter_crops(f) || f.radius > 0.0; }
+
+// The input filters (gicp_filter.hip) of the device cloud d_in [n][dim] with bounds mn / mx: the
+// crop, then radius outlier removal among its survivors.  The last stage in force writes to d_last when given
+// (else, as every other stage, to a buffer of the scratch).  track: also the input row of each survivor;
+// d_cnt: [n] device, prefilled -1, takes the exact count of every row the crop kept (and makes the count kernel
+// count to the end).  One stream sync per stage in force; the result words (bounds, M) are all that returns.
+FilterOut filter_stages(BuildScratch& bs, double* d_in, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3],
+                        const gicp_filter& f, double* d_last, bool track, int32_t* d_cnt, hipStream_t st) {
+    FilterOut fo;
+    fo.pts = d_in;
+    fo.M = n;
+    for (int a = 0; a < 3; ++a) fo.mn[a] = mn[a], fo.mx[a] = mx[a];
+    const bool crop = filter_crops(f), ror = f.radius > 0.0;
+    if (!crop && !ror) return fo;
+    bs.f_keep.reserve((size_t)n);
+    bs.f_pos.reserve((size_t)n);
+    if (!bs.v_res) bs.v_res.alloc((size_t)kVoxelRes);
+    auto dest = [&](int k, bool last) -> double* {
+        if (last && d_last) return d_last;
+        bs.f_pts[k].reserve((size_t)n * dim);
+        return bs.f_pts[k];
+    };
+    auto index = [&](int k) -> int32_t* {
+        if (!track) return nullptr;
+        bs.f_idx[k].reserve((size_t)n);
+        return bs.f_idx[k];
+    };
+    unsigned long long res[kVoxelRes];
+    if (crop) {
+        size_t tmp_bytes = 0;
+        HIPCHK(voxel_temp_bytes(n, 1, &tmp_bytes, st));
+        bs.v_tmp.reserve(tmp_bytes + 16);
+        CropArgs ca{};
+        ca.in = d_in;
+        ca.n = n;
+        ca.dim = dim;
+        for (int a = 0; a < 3; ++a) ca.center[a] = a < dim ? f.center[a] : 0.0;
+        ca.lo2 = f.min_range * f.min_range;
+        ca.hi2 = f.max_range * f.max_range;
+        ca.keep = bs.f_keep;
+        ca.pos1 = bs.f_pos;
+        ca.tmp = bs.v_tmp;
+        ca.tmp_bytes = tmp_bytes;
+        ca.out = dest(0, !ror);
+        ca.idx_out = index(0);
+        ca.res = bs.v_res;
+        HIPCHK(launch_crop(ca, st));
+        read_result_words(bs, res, st);
+        fo.M = (int64_t)res[6];
+        if (fo.M <= 0) fail_filter_empty(0, n, f);
+        decode_bounds(res, dim, fo.mn, fo.mx);
+        fo.pts = ca.out;
+        fo.idx = ca.idx_out;
+    }
+    if (ror) {
+        const int64_t m = fo.M;
+        VoxelArgs va{};
+        RorArgs ra{};
+        va.raw = fo.pts;
+        va.n = m;
+        va.dim = dim;
+        va.min_points = 1;
+        va.end_bit = ror_key_bits(dim, fo.mn, fo.mx, f.radius, va.leaf, va.cmin, va.bits, ra.cmax);
+        bs.v_keys.reserve((size_t)m);
+        bs.v_keys2.reserve((size_t)m);
+        bs.v_idx.reserve((size_t)m);
+        bs.v_idx2.reserve((size_t)m);
+        bs.f_packed.reserve((size_t)m * dim);
+        size_t tmp_bytes = 0;
+        HIPCHK(voxel_temp_bytes(m, va.end_bit, &tmp_bytes, st));
+        bs.v_tmp.reserve(tmp_bytes + 16);
+        va.keys = bs.v_keys;
+        va.keys_s = bs.v_keys2;
+        va.idx = bs.v_idx;
+        va.idx_s = bs.v_idx2;
+        va.tmp = bs.v_tmp;
+        va.tmp_bytes = tmp_bytes;
+        va.res = bs.v_res;
+        ra.r2 = f.radius * f.radius;
+        ra.min_neighbors = f.min_neighbors;
+        ra.full = d_cnt ? 1 : 0;
+        ra.packed = bs.f_packed;
+        ra.keep = bs.f_keep;
+        ra.pos1 = bs.f_pos;
+        ra.idx_in = fo.idx;
+        ra.cnt_out = d_cnt;
+        ra.out = dest(1, true);
+        ra.idx_out = index(1);
+        HIPCHK(launch_ror(va, ra, st));
+        read_result_words(bs, res, st);
+        fo.M = (int64_t)res[6];
+        if (fo.M <= 0) fail_filter_empty(1, m, f);
+        decode_bounds(res, dim, fo.mn, fo.mx);
+        fo.pts = ra.out;
+        fo.idx = ra.idx_out;
+    }
+    return fo;
 }
 
 // De-skew the device cloud d_pts [n][dim] in place on `st` (gicp_sweep.hip): the host stamps are uploaded into
@@ -368,7 +475,26 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
         log.tick("deskew");
     };
     // (a staged build passes its pinned copy: the H2D copy is then asynchronous)
-    if (spec.voxel_leaf > 0.0) {
+    if (filter_on(spec.filter)) {
+        // upload, de-skew, crop, radius outlier removal, voxel filter, index: every stage hands the next one its
+        // survivors and their exact bounds on the device; the last input filter writes where the index reads
+        const bool voxel = spec.voxel_leaf > 0.0;
+        bs.v_raw.reserve((size_t)n * dim);
+        HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
+        log.tick("upload");
+        if (spec.sweep) deskew(bs.v_raw);
+        const FilterOut fo = filter_stages(bs, bs.v_raw, n, dim, mn, mx, spec.filter, voxel ? nullptr : bs.s_in.get(), false,
+                                           nullptr, st);
+        n = fo.M;
+        for (int a = 0; a < 3; ++a) mn[a] = fo.mn[a], mx[a] = fo.mx[a];
+        log.tick("filter");
+        if (voxel) {
+            const VoxelOut vo = voxel_filter(bs, fo.pts, n, dim, mn, mx, spec.voxel_leaf, spec.voxel_min, bs.s_in, st);
+            n = vo.M;
+            for (int a = 0; a < 3; ++a) mn[a] = vo.mn[a], mx[a] = vo.mx[a];
+            log.tick("voxel");
+        }
+    } else if (spec.voxel_leaf > 0.0) {
         bs.v_raw.reserve((size_t)n * dim);
         HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
         if (spec.sweep) deskew(bs.v_raw);
@@ -389,6 +515,7 @@ BuildSpec target_spec(const gicp_ctx* c, hipStream_t st) {
     spec.graph = c->use_graph && c->use_certs;
     spec.voxel_leaf = c->voxel_leaf;
     spec.voxel_min = c->voxel_min;
+    spec.filter = c->filt;
     spec.stream = st;
     return spec;
 }
@@ -401,6 +528,7 @@ BuildSpec source_spec(const gicp_ctx* c, int shard, int nshards) {
     spec.tile_points = c->src_tile;
     spec.voxel_leaf = c->voxel_leaf;
     spec.voxel_min = c->voxel_min;
+    spec.filter = c->filt;
     spec.stream = c->stream;
     return spec;
 }
@@ -447,6 +575,45 @@ void voxel_downsample(gicp_ctx* c, const double* xyz, int64_t N, int dim, double
     if (out_count) HIPCHK(hipMemcpyAsync(out_count, bs.v_ocnt, sizeof(int32_t) * vo.M, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     *M_out = vo.M;
+}
+
+// gicp_filter_points: the one-shot of the input filters, host in, host out
+void filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gicp_filter& f, double* out_xyz, int64_t* out_index,
+                   int32_t* out_count, int64_t* M_out) {
+    double mn[3], mx[3];
+    scan_bounds(xyz, N, dim, mn, mx);
+    if (!filter_on(f)) {   // the identity
+        std::memcpy(out_xyz, xyz, sizeof(double) * N * dim);
+        for (int64_t i = 0; i < N; ++i) {
+            if (out_index) out_index[i] = i;
+            if (out_count) out_count[i] = 0;
+        }
+        *M_out = N;
+        return;
+    }
+    BuildScratch& bs = c->bs;
+    hipStream_t st = c->stream;
+    bs.v_raw.reserve((size_t)N * dim);
+    HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * N * dim, hipMemcpyHostToDevice, st));
+    const bool counts = out_count && f.radius > 0.0;
+    if (counts) {
+        bs.f_cnt.reserve((size_t)N);
+        HIPCHK(hipMemsetAsync(bs.f_cnt, 0xFF, sizeof(int32_t) * N, st));   // -1: removed by the crop
+    }
+    const bool track = out_index || out_count;
+    const FilterOut fo = filter_stages(bs, bs.v_raw, N, dim, mn, mx, f, nullptr, track, counts ? bs.f_cnt.get() : nullptr, st);
+    std::vector<int32_t> idx(track ? (size_t)fo.M : 0);
+    HIPCHK(hipMemcpyAsync(out_xyz, fo.pts, sizeof(double) * fo.M * dim, hipMemcpyDeviceToHost, st));
+    if (track) HIPCHK(hipMemcpyAsync(idx.data(), fo.idx, sizeof(int32_t) * fo.M, hipMemcpyDeviceToHost, st));
+    if (counts) HIPCHK(hipMemcpyAsync(out_count, bs.f_cnt, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (out_index)
+        for (int64_t m = 0; m < fo.M; ++m) out_index[m] = idx[m];
+    if (out_count && !counts) {   // the crop alone: 0 for a kept row, -1 for a removed one
+        for (int64_t i = 0; i < N; ++i) out_count[i] = -1;
+        for (int64_t m = 0; m < fo.M; ++m) out_count[idx[m]] = 0;
+    }
+    *M_out = fo.M;
 }
 
 // gicp_deskew: the sweep xyz with twist xi, de-skewed on the device into `out` (host)

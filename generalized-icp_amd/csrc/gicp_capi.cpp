@@ -82,7 +82,7 @@ void check_sweep_args(const double* xyz, const double* stamps, int64_t N, int di
 
 extern "C" {
 
-int gicp_version(void) { return 103; }
+int gicp_version(void) { return 104; }
 
 int gicp_stats_size(int dim) { return (dim == 2 || dim == 3) ? nstat(dim == 2 ? 2 : 3) : GICP_E_INVALID; }
 
@@ -477,6 +477,31 @@ int gicp_voxel_downsample(gicp_ctx* c, const double* xyz, int64_t N, int dim, do
         if (min_points < 1) throw Fail{GICP_E_INVALID, "min_points must be >= 1"};
         *M_out = 0;
         voxel_downsample(c, xyz, N, dim, leaf, min_points, out_xyz, out_count, M_out);
+    });
+}
+
+// ---- input filters; gicp_filter_points_host lives in gicp_hostmath.cpp ----
+
+int gicp_set_filter(gicp_ctx* c, const gicp_filter* f) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_set_filter", [&] {
+        gicp_filter v{};
+        if (f) {
+            check_filter(*f);
+            v = *f;
+            v.pad = 0;
+        }
+        c->filt = v;
+    });
+}
+
+int gicp_filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz,
+                       int64_t* out_index, int32_t* out_count, int64_t* M_out) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_filter_points", [&] {
+        check_filter_args(xyz, N, dim, f, out_xyz, M_out);
+        *M_out = 0;
+        filter_points(c, xyz, N, dim, *f, out_xyz, out_index, out_count, M_out);
     });
 }
 

@@ -1,0 +1,217 @@
+// gicp_filter.hip — the input filters on the MI355X (gfx950): range crop and radius outlier removal
+// (DESIGN.md §3o).  The predicates are gicp_filter.h's, the ones the host yardstick runs.
+//
+//   k_crop_flags     one lane per row: keep flag from d2(p, centre) against min_range^2 / max_range^2
+//   rocPRIM          inclusive scan of the flags -> output row + 1
+//   k_filter_compact kept rows to their output rows (their order is kept), the input row of each, the exact
+//                    min / max per axis by a wave reduction and one ordered-integer atomic per wave and axis, M
+//   ROR, on the crop's survivors:
+//   k_voxel_key      (gicp_voxel.hip) cell of every point on the absolute grid of edge radius kRorEdge, one key
+//   rocPRIM          stable radix sort of (key, row)
+//   k_ror_gather     the points in key order, packed: the pair loop reads contiguous rows
+//   k_ror_count<D>   the hot kernel: one lane per point IN KEY ORDER, so a wave's lanes share cells and their
+//                    candidate loads hit the same lines.  The key packs x high and the last axis low, so the cells
+//                    (c_x, c_y, c_z - 1 .. c_z + 1) are one run of sorted keys: 9 runs (2-D: 3) cover the 27 (9)
+//                    neighbour cells, each found by a lower and an upper bound and clipped at the axis ends -- a
+//                    run never reaches into the row (c_x, c_y +- 1), cells outside the grid are skipped, not
+//                    wrapped.  Integer counts; the keep flag and the count go back to the point's original row
+//   rocPRIM, k_filter_compact   as for the crop
+//
+// No floating-point atomics and no order-dependent sums: flags, counts and bounds are integers, so the output is
+// bit-identical from call to call and from context to context.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+#include "gicp_filter.h"
+#include "gicp_internal.h"
+
+namespace gicp {
+
+hipError_t launch_voxel_keys(const VoxelArgs& A, hipStream_t st);   // gicp_voxel.hip
+
+namespace {
+
+// doubles as unsigned integers of the same order (gicp_voxel.hip enc_ordered, gicp_hostmath.cpp dec_ordered)
+__device__ __forceinline__ unsigned long long enc_ordered(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) k_crop_flags(CropArgs A) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) {   // (stream order: long before k_filter_compact's atomics)
+        for (int a = 0; a < 3; ++a) {
+            A.res[a] = ~0ull;
+            A.res[3 + a] = 0ull;
+        }
+        A.res[6] = A.res[7] = 0ull;
+    }
+    if (i >= A.n) return;
+    double p[D];
+    for (int a = 0; a < D; ++a) p[a] = A.in[i * D + a];
+    A.keep[i] = crop_keeps(filter_d2<D>(p, A.center), A.lo2, A.hi2) ? 1 : 0;
+}
+
+// res[0..5] hold min = all ones, max = 0 and res[6] = 0 when this runs (k_crop_flags, k_voxel_key)
+template <int D>
+__global__ void __launch_bounds__(256) k_filter_compact(const double* __restrict__ in, int64_t n,
+                                                        const int32_t* __restrict__ keep, const int32_t* __restrict__ pos1,
+                                                        const int32_t* __restrict__ idx_in, double* __restrict__ out,
+                                                        int32_t* __restrict__ idx_out, unsigned long long* res) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool k = i < n && keep[i] != 0;
+    unsigned long long mn[D], mx[D];
+    for (int a = 0; a < D; ++a) mn[a] = ~0ull, mx[a] = 0ull;
+    if (k) {
+        const int64_t m = pos1[i] - 1;
+        for (int a = 0; a < D; ++a) {
+            const double v = in[i * D + a];
+            out[m * D + a] = v;
+            mn[a] = mx[a] = enc_ordered(v);
+        }
+        if (idx_out) idx_out[m] = idx_in ? idx_in[i] : (int32_t)i;
+    }
+    if (i == n - 1) res[6] = (unsigned long long)pos1[i];   // M
+    if (__ballot(k) == 0) return;
+    for (int a = 0; a < D; ++a) {
+#pragma unroll
+        for (int o = 1; o < kWave; o <<= 1) {
+            const unsigned long long a0 = __shfl_xor(mn[a], o), a1 = __shfl_xor(mx[a], o);
+            mn[a] = a0 < mn[a] ? a0 : mn[a];
+            mx[a] = a1 > mx[a] ? a1 : mx[a];
+        }
+        // A wave whose bounds cannot improve the words as it reads them sends no atomic.  The words only ever
+        // tighten, so a stale read is a looser bound and costs an atomic it did not need, never a skipped one:
+        // without the test every wave's six atomics queue on one line (1M rows: 94k of them, ~1 ms)
+        if ((threadIdx.x & 63) == 0) {
+            if (mn[a] < __atomic_load_n(&res[a], __ATOMIC_RELAXED)) atomicMin(&res[a], mn[a]);
+            if (mx[a] > __atomic_load_n(&res[3 + a], __ATOMIC_RELAXED)) atomicMax(&res[3 + a], mx[a]);
+        }
+    }
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) k_ror_gather(const double* __restrict__ in, const int32_t* __restrict__ idx_s,
+                                                    int64_t n, double* __restrict__ packed) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int64_t o = idx_s[j];
+    for (int a = 0; a < D; ++a) packed[j * D + a] = in[o * D + a];
+}
+
+// first sorted key >= k (Upper: > k) in ks[0 .. n)
+template <bool Upper>
+__device__ __forceinline__ int64_t key_bound(const uint64_t* __restrict__ ks, int64_t n, uint64_t k) {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        const uint64_t v = ks[mid];
+        if (Upper ? v <= k : v < k) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// One lane per point in key order.  Full = false: a lane stops at min_neighbors (its count is then a lower
+// bound that decides the same keep flag).
+template <int D, bool Full>
+__global__ void __launch_bounds__(256) k_ror_count(VoxelArgs V, RorArgs R) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= V.n) return;
+    const uint64_t* __restrict__ ks = V.keys_s;
+    const double* __restrict__ pk = R.packed;
+    const uint64_t key = ks[j];
+    double p[D];
+    for (int a = 0; a < D; ++a) p[a] = pk[j * D + a];
+    // the cells, relative to cmin: the last axis in the low bits
+    const int bl = V.bits[D - 1], bm = D == 3 ? V.bits[1] : 0;
+    const int64_t cl = (int64_t)(key & ((1ull << bl) - 1ull));
+    const int64_t cm = D == 3 ? (int64_t)((key >> bl) & ((1ull << bm) - 1ull)) : 0;
+    const int64_t ch = (int64_t)(key >> (bl + bm));
+    const int64_t l0 = cl > 0 ? cl - 1 : 0, l1 = cl < R.cmax[D - 1] ? cl + 1 : cl;   // (clipped at the axis ends)
+    int32_t count = 0;
+    bool done = false;
+    for (int dh = -1; dh <= 1 && !done; ++dh) {
+        const int64_t h = ch + dh;
+        if (h < 0 || h > R.cmax[0]) continue;
+        for (int dm = (D == 3 ? -1 : 0); dm <= (D == 3 ? 1 : 0) && !done; ++dm) {
+            const int64_t m = cm + dm;
+            if (D == 3 && (m < 0 || m > R.cmax[1])) continue;
+            const uint64_t row = (((uint64_t)h << bm) | (uint64_t)m) << bl;
+            const int64_t b = key_bound<false>(ks, V.n, row | (uint64_t)l0);
+            const int64_t e = key_bound<true>(ks, V.n, row | (uint64_t)l1);
+            for (int64_t t = b; t < e; ++t) {
+                if (t == j) continue;
+                double q[D];
+                for (int a = 0; a < D; ++a) q[a] = pk[t * D + a];
+                count += ror_near(filter_d2<D>(p, q), R.r2) ? 1 : 0;
+                if (!Full && count >= R.min_neighbors) {
+                    done = true;
+                    break;
+                }
+            }
+        }
+    }
+    const int64_t o = V.idx_s[j];
+    R.keep[o] = count >= R.min_neighbors ? 1 : 0;
+    if (Full && R.cnt_out) R.cnt_out[R.idx_in ? R.idx_in[o] : o] = count;
+}
+
+inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
+
+template <int D>
+hipError_t compact(const double* in, int64_t n, int32_t* keep, int32_t* pos1, void* tmp, size_t tmp_bytes,
+                   const int32_t* idx_in, double* out, int32_t* idx_out, unsigned long long* res, hipStream_t st) {
+    size_t tb = tmp_bytes;
+    hipError_t e = rocprim::inclusive_scan(tmp, tb, keep, pos1, (size_t)n, rocprim::plus<int32_t>(), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_filter_compact<D>, dim3(grid256(n)), dim3(256), 0, st, in, n, (const int32_t*)keep,
+                       (const int32_t*)pos1, idx_in, out, idx_out, res);
+    return hipGetLastError();
+}
+
+template <int D>
+hipError_t ror(const VoxelArgs& V, const RorArgs& R, hipStream_t st) {
+    const int64_t n = V.n;
+    const unsigned g = grid256(n);
+    hipError_t e = launch_voxel_keys(V, st);   // (also resets the result words)
+    if (e != hipSuccess) return e;
+    size_t tb = V.tmp_bytes;
+    e = rocprim::radix_sort_pairs(V.tmp, tb, V.keys, V.keys_s, V.idx, V.idx_s, (size_t)n, 0u, (unsigned)V.end_bit, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ror_gather<D>, dim3(g), dim3(256), 0, st, V.raw, (const int32_t*)V.idx_s, n, R.packed);
+    if (R.full) hipLaunchKernelGGL((k_ror_count<D, true>), dim3(g), dim3(256), 0, st, V, R);
+    else hipLaunchKernelGGL((k_ror_count<D, false>), dim3(g), dim3(256), 0, st, V, R);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return compact<D>(V.raw, n, R.keep, R.pos1, V.tmp, V.tmp_bytes, R.idx_in, R.out, R.idx_out, V.res, st);
+}
+
+}  // namespace
+
+// The crop on `st`: A.in [n][dim] -> A.out [M][dim], A.idx_out, A.res (bounds of the kept rows, M in res[6]).
+hipError_t launch_crop(const CropArgs& A, hipStream_t st) {
+    (void)hipGetLastError();
+    if (A.n <= 0 || (A.dim != 2 && A.dim != 3) || !A.in || !A.out || !A.keep || !A.pos1 || !A.res) return hipErrorInvalidValue;
+    const unsigned g = grid256(A.n);
+    if (A.dim == 3) {
+        hipLaunchKernelGGL(k_crop_flags<3>, dim3(g), dim3(256), 0, st, A);
+        return compact<3>(A.in, A.n, A.keep, A.pos1, A.tmp, A.tmp_bytes, nullptr, A.out, A.idx_out, A.res, st);
+    }
+    hipLaunchKernelGGL(k_crop_flags<2>, dim3(g), dim3(256), 0, st, A);
+    return compact<2>(A.in, A.n, A.keep, A.pos1, A.tmp, A.tmp_bytes, nullptr, A.out, A.idx_out, A.res, st);
+}
+
+// Radius outlier removal on `st`: V.raw [n][dim] -> R.out [M][dim], R.idx_out, R.cnt_out, V.res as for the crop.
+hipError_t launch_ror(const VoxelArgs& V, const RorArgs& R, hipStream_t st) {
+    (void)hipGetLastError();
+    if (V.n <= 0 || (V.dim != 2 && V.dim != 3) || V.end_bit < 1 || V.end_bit > 64 || !V.raw || !R.out || !R.packed ||
+        !R.keep || !R.pos1 || !V.res || R.min_neighbors < 1)
+        return hipErrorInvalidValue;
+    return V.dim == 3 ? ror<3>(V, R, st) : ror<2>(V, R, st);
+}
+
+}  // namespace gicp

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <memory>
 
+#include "gicp_filter.h"
 #include "gicp_hostmath.h"
 #include "gicp_sweep.h"
 
@@ -25,13 +26,15 @@ hipError_t launch_knn_cov(const CovArgs&, int, int, bool, hipStream_t);
 hipError_t launch_corr(const CorrArgs&, int, int, hipStream_t);
 hipError_t launch_solve(IterState*, int, hipStream_t, double*);
 hipError_t launch_peer_probe(const PeerArgs&, double*, hipStream_t);
-hipError_t launch_reset_tiles(int32_t*, int32_t*, float*, int32_t*, int, int32_t*, int64_t, hipStream_t);
+hipError_t launch_reset_tiles(int32_t*, int32_t*, float*, int32_t*, int, int32_t*, int64_t, double*, hipStream_t);
 hipError_t launch_graph_pack(const GraphArgs&, hipStream_t);
 hipError_t launch_rotate_cov(const double4*, const int32_t*, int64_t, int, const double*, double*, hipStream_t);
 hipError_t launch_top_weights(const double*, const int64_t*, const int32_t*, int64_t, int, double*, int64_t*, int, double*, int64_t*,
                               int64_t*, hipStream_t);
 hipError_t voxel_temp_bytes(int64_t, int, size_t*, hipStream_t);
 hipError_t launch_voxel(const VoxelArgs&, hipStream_t);
+hipError_t launch_crop(const CropArgs&, hipStream_t);
+hipError_t launch_ror(const VoxelArgs&, const RorArgs&, hipStream_t);
 hipError_t launch_points_out(const double*, const int32_t*, int64_t, int, double*, hipStream_t);
 hipError_t launch_deskew(const SweepArgs&, hipStream_t);
 hipError_t launch_eval(const EvalArgs&, hipStream_t);
@@ -152,6 +155,11 @@ struct BuildScratch {
     DevBuf<unsigned char> v_tmp;
     DevBuf<unsigned long long> v_res;
     DevBuf<double> w_stamps;          // the stamps of a sweep (gicp_sweep.hip)
+    // input filters (gicp_filter.hip): two clouds the stages alternate between, the points in key order, keep
+    // flags and their scan, the original row of each survivor after each stage, the counts (one-shot only); the
+    // keys, the sort's scratch and the result words are the voxel filter's
+    DevBuf<double> f_pts[2], f_packed;
+    DevBuf<int32_t> f_keep, f_pos, f_idx[2], f_cnt;
     std::unique_ptr<WorkerPool> pool;  // tiling threads (lazily started)
     WorkerPool& workers() {
         if (!pool) {
@@ -190,6 +198,8 @@ struct BuildSpec {
     // voxel filter, on the device), and the index is built over those centroids in key order
     double voxel_leaf = 0.0;
     int voxel_min = 1;
+    // the input filters, run after the de-skew and before the voxel filter; all-zero: off
+    gicp_filter filter{};
     // sweep: the uploaded cloud is first de-skewed on the device, point i moved by
     // Exp((stamps[i] - ref) Log(motion)); the filter and the index then see the de-skewed points and their bounds.
     // The twist is taken from `motion` ((dim+1)^2 row-major) once the build has begun, so a motion it refuses
@@ -214,7 +224,7 @@ struct BuildLog {
         HIPCHK(hipStreamSynchronize(st));
         const auto t = std::chrono::steady_clock::now();
         char b[64];
-        std::snprintf(b, sizeof b, " %s %.1f", what, std::chrono::duration<double, std::milli>(t - prev).count());
+        std::snprintf(b, sizeof b, " %s %.3f", what, std::chrono::duration<double, std::milli>(t - prev).count());
         text += b;
         prev = t;
     }
@@ -274,6 +284,7 @@ struct gicp_ctx {
     // voxel filter of every later cloud build (gicp_set_voxel): leaf 0 = off
     double voxel_leaf = 0.0;
     int voxel_min = 1;
+    gicp_filter filt{};               // input filters of every later cloud build (gicp_set_filter): all-zero = off
     gicp::VoxelMap map;               // local voxel map (gicp_map_reset)
     // staged targets (gicp_stage_target / gicp_commit_target): a ring of GICP_MAX_STAGED slots, each
     // built into its own cloud on its own stream by a host thread while the current target is
@@ -372,6 +383,8 @@ void copy_covariances(gicp_ctx* c, Cloud& cl, const double* R, double* out);
 void copy_points(gicp_ctx* c, Cloud& cl, double* out);
 void voxel_downsample(gicp_ctx* c, const double* xyz, int64_t N, int dim, double leaf, int min_points, double* out_xyz,
                       int32_t* out_count, int64_t* M_out);
+void filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gicp_filter& f, double* out_xyz, int64_t* out_index,
+                   int32_t* out_count, int64_t* M_out);
 void deskew_cloud(gicp_ctx* c, const double* xyz, const double* stamps, int64_t N, int dim, const double* xi, double ref,
                   double* out);
 void map_insert(gicp_ctx* c, const Cloud* cl, const double* xyz, int64_t n, const double* T);

@@ -9,6 +9,7 @@
 #include <new>
 #include <type_traits>
 
+#include "gicp_filter.h"
 #include "gicp_sweep.h"
 
 namespace gicp {
@@ -408,6 +409,166 @@ void deskew_host(const double* xyz, const double* stamps, int64_t n, int dim, co
         for (int64_t i = 0; i < n; ++i) sweep_point<2>(xi, stamps[i] - ref, xyz + i * 2, out + i * 2);
 }
 
+// ---- input filters (gicp_filter.h) ----
+
+// what gicp_set_filter, gicp_filter_points and gicp_filter_points_host refuse alike
+void check_filter(const gicp_filter& f) {
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(f.center[a])) throw Fail{GICP_E_INVALID, "filter: center is not finite"};
+    if (!std::isfinite(f.min_range) || !std::isfinite(f.max_range) || !std::isfinite(f.radius))
+        throw Fail{GICP_E_INVALID, "filter: min_range, max_range and radius must be finite"};
+    if (f.min_range < 0.0 || f.max_range < 0.0 || f.radius < 0.0)
+        throw Fail{GICP_E_INVALID, "filter: min_range, max_range and radius must be >= 0 (0 turns each off)"};
+    if (f.max_range > 0.0 && f.min_range > f.max_range) {
+        char b[128];
+        std::snprintf(b, sizeof b, "filter: min_range %g exceeds max_range %g", f.min_range, f.max_range);
+        throw Fail{GICP_E_INVALID, b};
+    }
+    if (f.radius > 0.0 && f.min_neighbors < 1) throw Fail{GICP_E_INVALID, "filter: min_neighbors must be >= 1 with a radius"};
+}
+
+bool filter_crops(const gicp_filter& f) { return f.min_range > 0.0 || f.max_range > 0.0; }
+
+// a stage left no row (stage 0: the crop of n rows, 1: radius outlier removal of the n rows the crop left)
+void fail_filter_empty(int stage, int64_t n, const gicp_filter& f) {
+    char b[200];
+    if (stage == 0)
+        std::snprintf(b, sizeof b, "filter: the range crop removed all %lld points (min_range %g, max_range %g)", (long long)n,
+                      f.min_range, f.max_range);
+    else
+        std::snprintf(b, sizeof b,
+                      "filter: radius outlier removal removed all %lld points the crop left (radius %g, min_neighbors %d)",
+                      (long long)n, f.radius, (int)f.min_neighbors);
+    throw Fail{GICP_E_INVALID, b};
+}
+
+// The grid of radius outlier removal over the cropped cloud's bounds.  The limit is stated in cells of edge
+// `radius`; the keys are those of the voxel filter's grid with leaf = radius kRorEdge (gicp_filter.h), which spans
+// no more cells.  Returns the bits the sort covers; cmax: the highest cell per axis relative to cmin.
+int ror_key_bits(int dim, const double (&mn)[3], const double (&mx)[3], double radius, double& leaf, double (&cmin)[3],
+                 int32_t (&bits)[3], int64_t (&cmax)[3]) {
+    const double lim = dim == 3 ? 2097152.0 : 2147483648.0;   // 2^21, 2^31 cells per axis
+    for (int a = 0; a < dim; ++a) {
+        const double c0 = std::floor(mn[a] / radius), c1 = std::floor(mx[a] / radius);
+        const double range = c1 - c0 + 1.0;
+        char b[224];
+        if (!(range <= lim)) {
+            std::snprintf(b, sizeof b,
+                          "filter: radius grid too wide: axis %c spans %.6g cells of edge radius = %g (at most 2^%d per axis in "
+                          "%d-D); crop the far returns first with a max_range",
+                          "xyz"[a], range, radius, dim == 3 ? 21 : 31, dim);
+            throw Fail{GICP_E_INVALID, b};
+        }
+        if (!(std::fabs(c0) < 34359738368.0 && std::fabs(c1) < 34359738368.0)) {   // 2^35: see kRorEdge
+            std::snprintf(b, sizeof b, "filter: axis %c lies beyond 2^35 cells of edge radius = %g from the origin", "xyz"[a],
+                          radius);
+            throw Fail{GICP_E_INVALID, b};
+        }
+    }
+    leaf = radius * kRorEdge;
+    const int end_bit = voxel_key_bits(dim, mn, mx, leaf, cmin, bits);
+    for (int a = 0; a < 3; ++a) cmax[a] = a < dim ? (int64_t)(std::floor(mx[a] / leaf) - cmin[a]) : 0;
+    return end_bit;
+}
+
+namespace {
+
+// The host yardstick: the device's algorithm as plain loops -- keys of the same grid, one sort, and per point the
+// same clipped key runs searched in the sorted keys.
+template <int D>
+void filter_host(const double* xyz, int64_t N, const gicp_filter& f, double* out_xyz, int64_t* out_index, int32_t* out_count,
+                 int64_t* M_out) {
+    std::vector<int64_t> rows;   // survivors of the crop, ascending
+    rows.reserve((size_t)N);
+    const double lo2 = f.min_range * f.min_range, hi2 = f.max_range * f.max_range;
+    for (int64_t i = 0; i < N; ++i) {
+        const bool k = !filter_crops(f) || crop_keeps(filter_d2<D>(xyz + i * D, f.center), lo2, hi2);
+        if (k) rows.push_back(i);
+        if (out_count) out_count[i] = k ? 0 : -1;
+    }
+    if (rows.empty()) fail_filter_empty(0, N, f);
+    const int64_t m = (int64_t)rows.size();
+    std::vector<char> keep((size_t)m, 1);
+    if (f.radius > 0.0) {
+        double mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+        for (int a = 0; a < D; ++a) mn[a] = mx[a] = xyz[rows[0] * D + a];
+        for (int64_t s = 0; s < m; ++s)
+            for (int a = 0; a < D; ++a) {
+                const double v = xyz[rows[s] * D + a];
+                mn[a] = v < mn[a] ? v : mn[a];
+                mx[a] = v > mx[a] ? v : mx[a];
+            }
+        double leaf, cmin[3];
+        int32_t bits[3];
+        int64_t cmax[3];
+        ror_key_bits(D, mn, mx, f.radius, leaf, cmin, bits, cmax);
+        std::vector<std::pair<uint64_t, int64_t>> ks((size_t)m);   // (key, survivor)
+        for (int64_t s = 0; s < m; ++s) {
+            uint64_t key = 0;
+            for (int a = 0; a < D; ++a)
+                key = (key << bits[a]) | (uint64_t)(int64_t)(std::floor(xyz[rows[s] * D + a] / leaf) - cmin[a]);
+            ks[s] = {key, s};
+        }
+        std::sort(ks.begin(), ks.end());
+        const double r2 = f.radius * f.radius;
+        const int bl = bits[D - 1], bm = D == 3 ? bits[1] : 0;
+        auto first = [&](uint64_t k) { return std::lower_bound(ks.begin(), ks.end(), std::make_pair(k, (int64_t)-1)) - ks.begin(); };
+        for (int64_t j = 0; j < m; ++j) {
+            const uint64_t key = ks[j].first;
+            const double* p = xyz + rows[ks[j].second] * D;
+            const int64_t cl = (int64_t)(key & ((1ull << bl) - 1ull));
+            const int64_t cm = D == 3 ? (int64_t)((key >> bl) & ((1ull << bm) - 1ull)) : 0;
+            const int64_t ch = (int64_t)(key >> (bl + bm));
+            const int64_t l0 = cl > 0 ? cl - 1 : 0, l1 = cl < cmax[D - 1] ? cl + 1 : cl;
+            int32_t count = 0;
+            for (int dh = -1; dh <= 1; ++dh) {
+                const int64_t h = ch + dh;
+                if (h < 0 || h > cmax[0]) continue;
+                for (int dm = (D == 3 ? -1 : 0); dm <= (D == 3 ? 1 : 0); ++dm) {
+                    const int64_t mm = cm + dm;
+                    if (D == 3 && (mm < 0 || mm > cmax[1])) continue;
+                    const uint64_t row = (((uint64_t)h << bm) | (uint64_t)mm) << bl;
+                    const int64_t b = first(row | (uint64_t)l0), e = first((row | (uint64_t)l1) + 1);
+                    for (int64_t t = b; t < e; ++t)
+                        if (t != j && ror_near(filter_d2<D>(p, xyz + rows[ks[t].second] * D), r2)) ++count;
+                }
+            }
+            const int64_t s = ks[j].second;
+            keep[s] = count >= f.min_neighbors;
+            if (out_count) out_count[rows[s]] = count;
+        }
+    }
+    int64_t M = 0;
+    for (int64_t s = 0; s < m; ++s) {
+        if (!keep[s]) continue;
+        for (int a = 0; a < D; ++a) out_xyz[M * D + a] = xyz[rows[s] * D + a];
+        if (out_index) out_index[M] = rows[s];
+        ++M;
+    }
+    if (M == 0) fail_filter_empty(1, m, f);
+    *M_out = M;
+}
+
+}  // namespace
+
+// the argument checks of both one-shot entry points, and the finiteness test
+void check_filter_args(const double* xyz, int64_t N, int dim, const gicp_filter* f, const double* out_xyz, const int64_t* M_out) {
+    check_cloud_args(xyz, N, dim);
+    if (!f) throw Fail{GICP_E_INVALID, "filter must not be NULL"};
+    if (!out_xyz || !M_out) throw Fail{GICP_E_INVALID, "out_xyz and M_out must not be NULL"};
+    check_filter(*f);
+    double mn[3], mx[3];
+    scan_bounds(xyz, N, dim, mn, mx);
+}
+
+void filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz, int64_t* out_index,
+                        int32_t* out_count, int64_t* M_out) {
+    check_filter_args(xyz, N, dim, f, out_xyz, M_out);
+    *M_out = 0;
+    if (dim == 3) filter_host<3>(xyz, N, *f, out_xyz, out_index, out_count, M_out);
+    else filter_host<2>(xyz, N, *f, out_xyz, out_index, out_count, M_out);
+}
+
 // ---- what every entry point checks the same way ----
 
 void check_cloud_args(const double* xyz, int64_t n, int dim) {
@@ -597,3 +758,31 @@ int current_failure(std::string& msg) {
 }
 
 }  // namespace gicp
+
+// The host-only filter lives here, not in gicp_capi.cpp, so that it links without the runtime
+// (tests/native/filter_check.cpp).  Its message goes to a per-thread string: it has no context to leave it in.
+namespace {
+thread_local std::string t_host_err;
+}
+
+extern "C" {
+
+int gicp_filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz, int64_t* out_index,
+                            int32_t* out_count, int64_t* M_out) {
+    try {
+        gicp::filter_points_host(xyz, N, dim, f, out_xyz, out_index, out_count, M_out);
+        return GICP_OK;
+    } catch (...) {
+        std::string msg;
+        const int rc = gicp::current_failure(msg);
+        try {
+            t_host_err = "gicp_filter_points_host: " + msg;
+        } catch (...) {
+        }
+        return rc == GICP_E_NOMEM ? GICP_E_INVALID : rc;
+    }
+}
+
+const char* gicp_last_host_error(void) { return t_host_err.c_str(); }
+
+}  // extern "C"

@@ -109,6 +109,16 @@ int64_t map_window_lo(int axis, double t, double leaf, int64_t R);
 void motion_twist(int dim, const double* M, double* xi);
 void deskew_host(const double* xyz, const double* stamps, int64_t n, int dim, const double* xi, double ref, double* out);
 
+// input filters: the setting's checks, the grid of radius outlier removal, the host yardstick
+void check_filter(const gicp_filter& f);
+bool filter_crops(const gicp_filter& f);
+[[noreturn]] void fail_filter_empty(int stage, int64_t n, const gicp_filter& f);
+int ror_key_bits(int dim, const double (&mn)[3], const double (&mx)[3], double radius, double& leaf, double (&cmin)[3],
+                 int32_t (&bits)[3], int64_t (&cmax)[3]);
+void check_filter_args(const double* xyz, int64_t N, int dim, const gicp_filter* f, const double* out_xyz, const int64_t* M_out);
+void filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz, int64_t* out_index,
+                        int32_t* out_count, int64_t* M_out);
+
 // registration report: information matrix of a pass's statistics, symmetric eigensolver
 void information(int dim, const double* stats, const double* T, double* H, double* b);
 void sym_eig(int n, const double* A, double* w, double* V);

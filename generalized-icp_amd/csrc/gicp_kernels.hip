@@ -3201,9 +3201,14 @@ hipError_t launch_corr(const CorrArgs& a, int dim, int grid, hipStream_t st) {
 }
 
 // reset_tile_state's per-source-tile and per-point resets in one launch
+// pose0: slot 0 of the pose ring.  Pass ids restart at 1, so the first pass's "displacement over the last pass"
+// (k_corr disp_since(pass - 1)) reads slot 0, which no pass since the reset has written: it is zeroed here, what a
+// fresh allocation holds, so that the first lists' skin does not depend on what the memory held before.
 __global__ void __launch_bounds__(256) k_reset_tiles(int32_t* hint, int32_t* list_len, float* list_rcert,
-                                                     int32_t* cert_pass, int nt, int32_t* cert_j, int64_t n) {
+                                                     int32_t* cert_pass, int nt, int32_t* cert_j, int64_t n, double* pose0) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && pose0)
+        for (int k = 0; k < 12; ++k) pose0[k] = 0.0;
     if (i < nt) {
         hint[i] = -1;
         list_len[i] = 0;
@@ -3214,12 +3219,12 @@ __global__ void __launch_bounds__(256) k_reset_tiles(int32_t* hint, int32_t* lis
 }
 
 hipError_t launch_reset_tiles(int32_t* hint, int32_t* list_len, float* list_rcert, int32_t* cert_pass, int nt,
-                              int32_t* cert_j, int64_t n, hipStream_t st) {
+                              int32_t* cert_j, int64_t n, double* pose0, hipStream_t st) {
     clear_foreign_error();
     const int64_t m = std::max<int64_t>(nt, n);
     if (m <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_reset_tiles, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, hint, list_len, list_rcert,
-                       cert_pass, nt, cert_j, n);
+                       cert_pass, nt, cert_j, n, pose0);
     return hipGetLastError();
 }
 

@@ -354,6 +354,15 @@ hipError_t voxel_temp_bytes(int64_t n, int end_bit, size_t* bytes, hipStream_t s
     return hipSuccess;
 }
 
+// The keys alone (radius outlier removal, gicp_filter.hip, sorts the same grid): A.raw, n, dim, leaf, cmin, bits ->
+// A.keys, A.idx = 0 .. n - 1; A.res is reset as launch_voxel resets it.
+hipError_t launch_voxel_keys(const VoxelArgs& A, hipStream_t st) {
+    (void)hipGetLastError();
+    if (A.n <= 0 || (A.dim != 2 && A.dim != 3) || !A.raw || !A.keys || !A.idx || !A.res) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_voxel_key, dim3(grid256(A.n)), dim3(256), 0, st, A);
+    return hipGetLastError();
+}
+
 // The whole filter on `st`: A.raw [n][dim] -> A.out_xyz [M][dim], A.out_cnt [M], A.res (kVoxelRes words:
 // ordered-integer min[3], max[3] of the surviving centroids, M, the number of occupied voxels).
 hipError_t launch_voxel(const VoxelArgs& A, hipStream_t st) {

@@ -22,7 +22,7 @@ from . import _lib
 from ._lib import Debug, Params, Report, ReportSpec, Result, Trace, check, dptr
 
 __all__ = ["gicp", "apply_transformation", "Engine", "RotatedCovariances", "expand_stats", "stats_size",
-           "default_params", "last_result", "voxel_downsample", "deskew", "deskew_host", "motion_twist", "information",
+           "default_params", "last_result", "voxel_downsample", "filter_points", "filter_points_host", "deskew", "deskew_host", "motion_twist", "information",
            "sym_eig"]
 
 
@@ -130,6 +130,7 @@ class Engine:
         self._hook = None          # keeps the ctypes callback of set_allreduce alive
         self._hook_fn = None       # (fn, nranks, rank) of that hook, to restore it after a gicp() call
         self.voxel = (0.0, 1)      # (voxel_size, min_points) of set_voxel; size 0: no filter
+        self.filter = _NO_FILTER   # the keywords of set_filter in force (all zero: no filter)
         self.map_dim = None        # dimension of the local voxel map (map_reset)
 
     def close(self):
@@ -217,7 +218,7 @@ class Engine:
             rc = self._lib.gicp_set_target_sweep(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), C.byref(sw))
         check(rc, self._ctx, "gicp_set_target")
         self.n_tgt, self.dim = a.shape
-        if self.voxel[0] > 0:
+        if self._reduces():
             self.n_tgt = self.cloud_size("target")
 
     def set_source(self, pts, params=None, shard=0, nshards=1, stamps=None, motion=None, ref=0.0):
@@ -232,7 +233,7 @@ class Engine:
                                                  C.byref(sw))
         check(rc, self._ctx, "gicp_set_source")
         self.n_src, self.dim = a.shape
-        if self.voxel[0] > 0:
+        if self._reduces():
             self.n_src = self.cloud_size("source")
         self.generation += 1
 
@@ -263,7 +264,7 @@ class Engine:
             rc = self._lib.gicp_stage_target_sweep(self._ctx, dptr(a), a.shape[0], a.shape[1], C.byref(p), flags,
                                                    C.byref(sw))
         check(rc, self._ctx, "gicp_stage_target")
-        self._staged.append((a.shape, p, (a, st) if borrow else None, self.voxel[0] > 0))
+        self._staged.append((a.shape, p, (a, st) if borrow else None, self._reduces()))
 
     def commit_target(self, shard=0, nshards=1):
         """Wait for the oldest staged target; the current target becomes the source, the staged one the target."""
@@ -274,7 +275,7 @@ class Engine:
             self.n_src = self.n_tgt
             self.generation += 1
         self.n_tgt, self.dim = staged[0]
-        if staged[3]:   # staged with a voxel filter set: the target holds the filtered cloud
+        if staged[3]:   # staged with a voxel or input filter set: the target holds the filtered cloud
             self.n_tgt = self.cloud_size("target")
 
     def cancel_stage(self):
@@ -292,6 +293,32 @@ class Engine:
         size = 0.0 if voxel_size is None else float(voxel_size)
         check(self._lib.gicp_set_voxel(self._ctx, size, int(min_points)), self._ctx, "gicp_set_voxel")
         self.voxel = (size, int(min_points))
+
+    def _reduces(self):
+        """A filter of the builds is in force (set_voxel, set_filter): a cloud then holds fewer rows than its input."""
+        return self.voxel[0] > 0 or _filter_on(self.filter)
+
+    def set_filter(self, center=None, min_range=0.0, max_range=0.0, radius=0.0, min_neighbors=1):
+        """Input filters of every cloud set or staged from now on (gicp_set_filter), on the device,
+        after the de-skew and before the voxel filter: a range crop about `center` (None: the origin, the sensor
+        of a scan in its own frame) keeping min_range <= |p - center| <= max_range (0: no limit), then radius
+        outlier removal among the crop's survivors, keeping a point with at least min_neighbors others within
+        `radius` (0: off).  Every argument at its default turns the filters off.  With a filter, every per-point
+        output of this engine refers to the rows of the FILTERED clouds, which points() returns: the input's
+        rows that survive, in their order.  Engine.filter holds the setting as these keywords."""
+        kw = _filter_kw(center, min_range, max_range, radius, min_neighbors)
+        f = _filter_struct(kw, None)
+        check(self._lib.gicp_set_filter(self._ctx, C.byref(f)), self._ctx, "gicp_set_filter")
+        self.filter = kw
+
+    def filter_points(self, points, center=None, min_range=0.0, max_range=0.0, radius=0.0, min_neighbors=1,
+                      return_index=False, return_counts=False):
+        """gicp.filter_points on this engine's GPU (gicp_filter_points); the engine's clouds and its set_filter
+        setting are untouched."""
+        a = self._cloud(points)
+        f = _filter_struct(_filter_kw(center, min_range, max_range, radius, min_neighbors), a.shape[1])
+        return _filter_call(lambda *args: check(self._lib.gicp_filter_points(self._ctx, *args), self._ctx,
+                                                "gicp_filter_points"), a, f, return_index, return_counts)
 
     def voxel_downsample(self, points, voxel_size, min_points=1, return_counts=False):
         """gicp.voxel_downsample on this engine's GPU (gicp_voxel_downsample); the engine's clouds and its
@@ -317,16 +344,16 @@ class Engine:
         return out
 
     def cloud_size(self, which="target"):
-        """Points the indexed cloud holds (gicp_cloud_size): the input's length, or with a voxel filter
-        the number of voxels kept."""
+        """Points the indexed cloud holds (gicp_cloud_size): the input's length, with set_filter the rows that
+        survive, with a voxel filter the number of voxels kept."""
         n = C.c_int64()
         check(self._lib.gicp_cloud_size(self._ctx, 0 if which == "target" else 1, C.byref(n)), self._ctx,
               "gicp_cloud_size")
         return int(n.value)
 
     def points(self, which="target"):
-        """The indexed cloud's points in its original order (gicp_get_points): the input rows, or with a
-        voxel filter the centroids every per-point output refers to."""
+        """The indexed cloud's points in its original order (gicp_get_points): the input rows, with set_filter
+        the surviving rows in their order, with a voxel filter the centroids -- what every per-point output refers to."""
         n = self.cloud_size(which)
         out = np.empty((n, self.dim))
         check(self._lib.gicp_get_points(self._ctx, 0 if which == "target" else 1, dptr(out)), self._ctx,
@@ -745,6 +772,52 @@ class RotatedCovariances(Sequence):
         return f"RotatedCovariances({len(self)} iterations x {len(self._init)} points)"
 
 
+_NO_FILTER = dict(center=None, min_range=0.0, max_range=0.0, radius=0.0, min_neighbors=1)
+
+
+def _filter_kw(center, min_range, max_range, radius, min_neighbors):
+    """The keywords of Engine.set_filter, normalised (None: the default of each)."""
+    return dict(center=None if center is None else tuple(float(v) for v in np.asarray(center, dtype=np.float64).ravel()),
+                min_range=0.0 if min_range is None else float(min_range),
+                max_range=0.0 if max_range is None else float(max_range),
+                radius=0.0 if radius is None else float(radius), min_neighbors=int(min_neighbors))
+
+
+def _filter_on(kw):
+    return kw["min_range"] > 0 or kw["max_range"] > 0 or kw["radius"] > 0
+
+
+def _filter_struct(kw, dim):
+    """gicp_filter of the keywords; dim: the cloud's dimension the centre must have (None: 2 or 3 values)."""
+    f = _lib.Filter()
+    c = kw["center"]
+    if c is not None:
+        if len(c) not in ((2, 3) if dim is None else (dim,)):
+            raise ValueError(f"center must hold {'2 or 3' if dim is None else dim} values, got {len(c)}")
+        for k, v in enumerate(c):
+            f.center[k] = v
+    f.min_range, f.max_range, f.radius = kw["min_range"], kw["max_range"], kw["radius"]
+    f.min_neighbors = kw["min_neighbors"]
+    return f
+
+
+def _filter_call(call, a, f, return_index, return_counts):
+    """One one-shot filter call (device or host) on the cloud `a`: the kept rows, then what was asked for."""
+    out = np.empty_like(a)
+    idx = np.empty(a.shape[0], dtype=np.int64) if return_index else None
+    cnt = np.empty(a.shape[0], dtype=np.int32) if return_counts else None
+    m = C.c_int64()
+    call(dptr(a), a.shape[0], a.shape[1], C.byref(f), dptr(out),
+         idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_index else None,
+         cnt.ctypes.data_as(C.POINTER(C.c_int32)) if return_counts else None, C.byref(m))
+    res = (out[:m.value].copy(),)
+    if return_index:
+        res += (idx[:m.value].copy(),)
+    if return_counts:
+        res += (cnt,)
+    return res[0] if len(res) == 1 else res
+
+
 def _engine(device):
     eng = _ENGINES.get(device)
     if eng is None:
@@ -761,6 +834,38 @@ def voxel_downsample(points, voxel_size, min_points=1, return_counts=False, devi
     not finite and positive, non-finite points, a cloud spanning more than 2^21 (3-D) / 2^31 (2-D) cells
     along an axis, and when no cell reaches min_points."""
     return _engine(int(device)).voxel_downsample(points, voxel_size, min_points, return_counts)
+
+
+def filter_points(points, center=None, min_range=0.0, max_range=0.0, radius=0.0, min_neighbors=1, return_index=False,
+                  return_counts=False, device=0):
+    """Range crop and radius outlier removal on the GPU (gicp_filter_points): keep the rows of
+    `points` (N x 2 or N x 3) with min_range <= |p - center| <= max_range (0: no limit; center None: the origin),
+    then, among those, the rows with at least min_neighbors others within `radius` (inclusive; 0: off).  The
+    decisions are those of the fp64 expression d2 = ((dx*dx + dy*dy) + dz*dz) against the squared bounds, every
+    operation rounded on its own, so NumPy's restatement gives the same rows.  Returns the kept rows in their
+    order; with return_index also their int64 rows in `points`; with return_counts also, per INPUT row, the int32
+    number of neighbours (-1 where the crop removed the row; 0 for kept rows without a radius).  Deterministic.
+    Raises ValueError for non-finite input or fields, negative ranges, min_range > max_range > 0,
+    min_neighbors < 1 with a radius, a stage that leaves no row, and a cropped cloud spanning more than 2^21
+    (3-D) / 2^31 (2-D) cells of edge radius along an axis (crop far returns with max_range first)."""
+    return _engine(int(device)).filter_points(points, center, min_range, max_range, radius, min_neighbors, return_index,
+                                              return_counts)
+
+
+def filter_points_host(points, center=None, min_range=0.0, max_range=0.0, radius=0.0, min_neighbors=1, return_index=False,
+                       return_counts=False):
+    """`filter_points` computed on the host by the same predicates (gicp_filter_points_host; no GPU needed): the
+    CPU yardstick, a plain loop."""
+    a = Engine._cloud(points)
+    f = _filter_struct(_filter_kw(center, min_range, max_range, radius, min_neighbors), a.shape[1])
+    lib = _lib.load()
+
+    def call(*args):
+        rc = lib.gicp_filter_points_host(*args)
+        if rc != _lib.GICP_OK:   # (host only: the message is the thread's, there is no context)
+            raise ValueError(lib.gicp_last_host_error().decode())
+
+    return _filter_call(call, a, f, return_index, return_counts)
 
 
 def deskew(points, stamps, motion, ref=0.0, device=0):
@@ -884,7 +989,8 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
          max_distance_nearest_neighbors=50, *, full_output=True, mode=None, inner=None, k_neighbors=None, device=0,
          devices=None, verbose=True, T0=None, method="plane_to_plane", transformation_epsilon=0.0,
          rotation_epsilon=0.0, euclidean_fitness_epsilon=0.0, mse_relative_epsilon=0.0, voxel_size=None,
-         voxel_min_points=1, robust_kernel=None, robust_scale=None):
+         voxel_min_points=1, robust_kernel=None, robust_scale=None, min_range=None, max_range=None, outlier_radius=None,
+         outlier_min_neighbors=1, filter_center=None):
     """Drop-in for gicp.py:78 — returns the same 7-tuple (gicp.py:174):
 
     (T, all_transformations, initial_source_cov_matrices, target_cov_matrices,
@@ -924,6 +1030,11 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
       points (voxel_downsample), and every per-point member of the 7-tuple -- the covariance arrays, the
       highest-weight points, all_source_cov_matrices -- refers to the FILTERED clouds, whose lengths
       differ from the inputs'.
+    min_range / max_range / outlier_radius / outlier_min_neighbors / filter_center: all None (default) registers
+      the clouds as given.  Otherwise both clouds first pass the input filters on the device
+      (Engine.set_filter: a range crop about filter_center, None the origin, then radius outlier removal), before
+      the voxel filter if voxel_size is given, and every per-point member of the 7-tuple -- the covariance
+      arrays, the highest-weight points, all_source_cov_matrices -- refers to the FILTERED clouds.
     robust_kernel / robust_scale: None (default) is plain least squares.  'huber', 'cauchy',
       'geman_mcclure' ('gm') or 'tukey' (or the GICP_ROBUST_* code) weights every accepted
       correspondence of a pass by the kernel's w(s / robust_scale), s = sqrt(r^T W r) the whitened residual
@@ -970,22 +1081,30 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
         e.set_target(tgt, p)
         e.set_source(src, p, shard=r, nshards=G)
 
-    if voxel_size is None:
+    filt = None
+    if not (min_range is None and max_range is None and outlier_radius is None):
+        filt = _filter_kw(filter_center, min_range, max_range, outlier_radius, outlier_min_neighbors)
+    if voxel_size is None and filt is None:
         _run_ranks(engines, build)
         eng = engines[0]
-    else:   # the engines are shared between calls: the setting lasts for this call's builds only
+    else:   # the engines are shared between calls: the settings last for this call's builds only
         prev_voxel = [e.voxel for e in engines]
+        prev_filter = [e.filter for e in engines]
         try:
             for e in engines:
-                e.set_voxel(voxel_size, voxel_min_points)
+                if voxel_size is not None:
+                    e.set_voxel(voxel_size, voxel_min_points)
+                if filt is not None:
+                    e.set_filter(**filt)
             _run_ranks(engines, build)
             eng = engines[0]
             # the host side of the loops (highest-weight points, the faithful mode's moved source) works on
             # the clouds the engine registers
             src, tgt = eng.points("source"), eng.points("target")
         finally:
-            for e, v in zip(engines, prev_voxel):
+            for e, v, f in zip(engines, prev_voxel, prev_filter):
                 e.set_voxel(*v)
+                e.set_filter(**f)
     target_cov = eng.covariances("target")
     init_src_cov = eng.covariances("source")
     for e in engines[1:]:   # each device computed its own shard's source covariances (NaN elsewhere)

@@ -118,6 +118,18 @@ class Sweep(C.Structure):
     ]
 
 
+class Filter(C.Structure):
+    """gicp_filter (include/gicp_hip.h): the range crop and radius outlier removal of a cloud."""
+    _fields_ = [
+        ("center", C.c_double * 3),
+        ("min_range", C.c_double),
+        ("max_range", C.c_double),
+        ("radius", C.c_double),
+        ("min_neighbors", C.c_int32),
+        ("pad", C.c_int32),
+    ]
+
+
 REPORT_MAX = 8
 
 
@@ -209,6 +221,12 @@ SIGNATURES = {
     "gicp_set_source_sweep": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.POINTER(Params), C.c_int, C.c_int,
                                         C.POINTER(Sweep)]),
     "gicp_stage_target_sweep": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.POINTER(Params), C.c_int, C.POINTER(Sweep)]),
+    "gicp_filter_points": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.POINTER(Filter), _DP, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "gicp_filter_points_host": (C.c_int, [_DP, C.c_int64, C.c_int, C.POINTER(Filter), _DP, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "gicp_last_host_error": (C.c_char_p, []),
+    "gicp_set_filter": (C.c_int, [_VP, C.POINTER(Filter)]),
     "gicp_map_reset": (C.c_int, [_VP, C.c_int, C.c_double, C.c_double]),
     "gicp_map_insert": (C.c_int, [_VP, C.c_int, _DP]),
     "gicp_map_insert_points": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, _DP]),
@@ -228,8 +246,8 @@ _lib = None
 # the sources gicp_build_info()'s hash covers, in the Makefile's HASH_SRCS order
 HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
              "csrc/gicp_build.cpp", "csrc/gicp_align.cpp", "csrc/gicp_exchange.cpp", "csrc/gicp_voxel.hip",
-             "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_internal.h", "csrc/gicp_mem.h", "csrc/gicp_sweep.h",
-             "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
+             "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_filter.hip", "csrc/gicp_internal.h", "csrc/gicp_mem.h",
+             "csrc/gicp_sweep.h", "csrc/gicp_filter.h", "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
              "../include/gicp_hip.h")
 
 

@@ -39,7 +39,8 @@ from . import Engine, default_params
 class Odometry:
     def __init__(self, dim=3, params=None, device=0, composition="se3", init="constant_velocity", borrow=False,
                  voxel_size=None, voxel_min_points=1, map_voxel_size=None, map_range=None, map_min_points=1,
-                 deskew=False, deskew_ref=0.5, report=None, **kw):
+                 deskew=False, deskew_ref=0.5, report=None, min_range=None, max_range=None, outlier_radius=None,
+                 outlier_min_neighbors=1, **kw):
         if composition not in ("se3", "reference"):
             raise ValueError("composition must be 'se3' or 'reference'")
         if init not in ("identity", "constant_velocity"):
@@ -66,6 +67,12 @@ class Odometry:
         # synchronous paths alike; a borrowed scan is still read in place
         if voxel_size is not None:
             self.eng.set_voxel(voxel_size, voxel_min_points)
+        # min_range / max_range / outlier_radius / outlier_min_neighbors: every scan first passes the input
+        # filters on the device (Engine.set_filter), after its de-skew and before the voxel filter: a range crop
+        # about the origin -- scans are in the sensor frame -- then radius outlier removal.  It drops the
+        # max-range and invalid returns that would stretch the cloud's extent
+        if not (min_range is None and max_range is None and outlier_radius is None):
+            self.eng.set_filter(None, min_range, max_range, outlier_radius, outlier_min_neighbors)
         self.composition = composition
         self.init = init
         # borrow=True: staged scans are read by the library in place (GICP_STAGE_BORROW, no copy on this

@@ -159,7 +159,8 @@ int gicp_version(void);                          /* 100 * major + minor; 101: gi
                                                     pad_robust, robust_scale (appended); 102: motion
                                                     compensation (gicp_sweep, gicp_deskew, gicp_*_sweep); 103: the
                                                     registration report (gicp_evaluate, gicp_information,
-                                                    gicp_sym_eig) */
+                                                    gicp_sym_eig); 104: the input filters (gicp_filter,
+                                                    gicp_filter_points[_host], gicp_set_filter) */
 int gicp_stats_size(int dim);                    /* 26 (dim 2) or 74 (dim 3) */
 void gicp_default_params(int dim, gicp_params* out);
 const char* gicp_strerror(int code);
@@ -205,8 +206,8 @@ int gicp_peer_close(gicp_ctx* ctx);   /* back to no exchange (RCCL / hook as set
 /* Build provenance of this library: "src=<first 16 hex of sha256 over the sources>;git=<rev>;built=<date
  * time>;arch=gfx950".  The source hash covers csrc/{gicp_kernels.hip, gicp_capi.cpp, gicp_solver.cpp,
  * gicp_cg.cpp, gicp_hostmath.cpp, gicp_build.cpp, gicp_align.cpp, gicp_exchange.cpp, gicp_voxel.hip, gicp_sweep.hip,
- * gicp_eval.hip, gicp_internal.h, gicp_mem.h, gicp_sweep.h, gicp_solver.h, gicp_solve_dev.h, gicp_hostmath.h,
- * gicp_host.h} and include/gicp_hip.h, concatenated in that order, so
+ * gicp_eval.hip, gicp_filter.hip, gicp_internal.h, gicp_mem.h, gicp_sweep.h, gicp_filter.h, gicp_solver.h,
+ * gicp_solve_dev.h, gicp_hostmath.h, gicp_host.h} and include/gicp_hip.h, concatenated in that order, so
  * a caller can prove the loaded library was compiled from the sources beside it. */
 const char* gicp_build_info(void);
 
@@ -442,6 +443,57 @@ int gicp_set_source_sweep(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, 
                           int nshards, const gicp_sweep* sweep);
 int gicp_stage_target_sweep(gicp_ctx* ctx, const double* xyz, int64_t M, int dim, const gicp_params* p, int flags,
                             const gicp_sweep* sweep);
+
+/* ---- input filters: range crop and radius outlier removal -----------------------------
+ * What a LiDAR front end runs before registration, on the device.  Two stages, in this order:
+ *   1. CROP.  Keep p iff d2(p, center) >= min_range * min_range (min_range > 0) and d2(p, center) <=
+ *      max_range * max_range (max_range > 0); a range of 0 sets no limit.
+ *   2. RADIUS OUTLIER REMOVAL among the crop's survivors only.  For survivor i,
+ *      count_i = #{ j != i, j a survivor : d2(p_i, p_j) <= radius * radius } -- the bound is inclusive, as d_c
+ *      is, and coincident other rows count -- and i is kept iff count_i >= min_neighbors.  One pass, not iterated.
+ * All arithmetic is fp64 and every product and every sum is rounded on its own (no FMA):
+ *   d2(a, b) = ((dx * dx + dy * dy) + dz * dz),  dx = a_x - b_x,  the z term dropped in 2-D,
+ * the same bits in either direction, and the bits NumPy's expression gives.  The same functions
+ * (csrc/gicp_filter.h) serve the device kernels and gicp_filter_points_host.  Survivors keep their original
+ * relative order.  A filter with every field 0 is the identity.  No floating-point atomics: the output is
+ * bit-identical from call to call and context to context.
+ * GICP_E_INVALID for: a non-finite field; a negative range or radius; min_range > max_range with max_range > 0;
+ * min_neighbors < 1 with radius > 0; non-finite input; a stage that leaves no row (the message names the stage);
+ * a cropped cloud that spans more than 2^21 (3-D) or 2^31 (2-D) cells of edge `radius` on an axis (the message
+ * names the axis and suggests a max_range) or lies beyond 2^35 such cells from the origin.
+ *
+ * One-shot, host in, host out: out_xyz [N][dim], out_index [N] (may be NULL) and out_count [N] (may be NULL) are
+ * caller-allocated; *M_out receives the number of rows kept (they come first).  out_index: the original row of
+ * each kept row, ascending.  out_count, per INPUT row: the exact count_i, -1 where the crop removed the row (0
+ * for every kept row when radius is 0).  With out_count == NULL a point stops counting at min_neighbors; the
+ * kept set is the same.  The context's clouds and its gicp_set_filter setting are untouched.
+ * gicp_filter_points_host is host only, as gicp_deskew_host: no HIP call, no context -- a plain cell-bucketed
+ * loop, the CPU yardstick, not a fast path.  Its message is gicp_last_host_error()'s (per thread).
+ *
+ * Context setting (gicp_set_filter; NULL or all-zero: off, the default): filters every later gicp_set_target /
+ * gicp_set_source / gicp_stage_target[_ex] cloud and their *_sweep forms on the device -- after the upload and
+ * the de-skew, so `center` is in the de-skewed sensor frame, and before the voxel filter (if set) and the index,
+ * which take the device's exact bounds of the survivors (one stream synchronisation per stage in force; only
+ * result words return to the host).  A staged build uses the setting in force when it was staged, on its own
+ * stream; GICP_STAGE_BORROW still reads the caller's raw frame in place.  With a sharded source every rank
+ * filters the whole cloud.  With a filter set, "original order" and "original index" of a cloud, everywhere in
+ * this header, mean the rows of the FILTERED cloud; gicp_cloud_size and gicp_get_points return their number and
+ * the rows.  A filter that fails after the build began (no survivor, a grid too wide) leaves that cloud NOT
+ * SET, as any failed build. */
+typedef struct gicp_filter {
+    double center[3];      /* crop centre, in the frame of the cloud (the sensor origin; 2-D uses two) */
+    double min_range;      /* >= 0; keep d2(p, c) >= min_range * min_range   (0: no lower limit) */
+    double max_range;      /* >= 0; keep d2(p, c) <= max_range * max_range   (0: no upper limit) */
+    double radius;         /* > 0: radius outlier removal on the cropped cloud; 0: off */
+    int32_t min_neighbors; /* >= 1 when radius > 0 */
+    int32_t pad;
+} gicp_filter;
+int gicp_filter_points(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz,
+                       int64_t* out_index, int32_t* out_count, int64_t* M_out);
+int gicp_filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz,
+                            int64_t* out_index, int32_t* out_count, int64_t* M_out);
+const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host ("" if none) */
+int gicp_set_filter(gicp_ctx* ctx, const gicp_filter* f);
 
 /* ---- local voxel map ----------------------------------------------------------------
  * A device-resident set of voxels of the same absolute grid as the filter above, in the WORLD frame: each

@@ -82,7 +82,7 @@ void check_sweep_args(const double* xyz, const double* stamps, int64_t N, int di
 
 extern "C" {
 
-int gicp_version(void) { return 104; }
+int gicp_version(void) { return 105; }
 
 int gicp_stats_size(int dim) { return (dim == 2 || dim == 3) ? nstat(dim == 2 ? 2 : 3) : GICP_E_INVALID; }
 

@@ -41,6 +41,9 @@ hipError_t launch_eval(const EvalArgs&, hipStream_t);
 hipError_t launch_map_insert(const VoxelArgs&, const MapArgs&, hipStream_t);
 hipError_t launch_map_centroids(const double*, int64_t, int, int, int32_t*, int32_t*, void*, size_t, double*,
                                 unsigned long long*, hipStream_t);
+hipError_t launch_batch_cov(const BatchCovArgs&, int, int, int, hipStream_t);
+hipError_t launch_batch_align(const BatchArgs&, int, int, hipStream_t);
+int batch_max_points(int dim);
 int corr_grid(int q_tiles, int shard, int nshards);
 int solve_pose(int d, const double* st, const double* Tk, double* Tout, double* loss_out);
 
@@ -362,6 +365,14 @@ struct gicp_ctx {
     gicp::DevBuf<double> d_trace_det;       // [iter][16]
     gicp::DevBuf<unsigned long long> d_tail;     // GICP_TAIL diagnostic build: [iter][kTailWords] (on this context's device)
     gicp::DevBuf<unsigned long long> d_stamps;   // GICP_STAMPS / GICP_TIMELINE diagnostic builds: [wave][20]
+    // gicp_batch_align: all clouds' points, the packed offsets / work list / problems / debug row
+    // starts, the covariances and counts of every row, the problems' outcomes, the optional debug outputs
+    gicp::DevBuf<double> b_xyz, b_dbg_cov, b_dbg_dist;
+    gicp::DevBuf<unsigned char> b_meta;
+    gicp::DevBuf<double4> b_cov;
+    gicp::DevBuf<int32_t> b_cnt;
+    gicp::DevBuf<gicp::BatchOut> b_out;
+    gicp::DevBuf<int64_t> b_dbg_idx;
     static constexpr int kMaxBatch = 64;
     hipEvent_t ev[2 * kMaxBatch] = {};
     int batch_hint = 0;               // iterations the last converging align ran: its first batch next time
@@ -400,6 +411,11 @@ void top_enqueue(gicp_ctx* c, int k);
 void run_pass(gicp_ctx* c, const double* T, gicp_debug* dbg, bool keep_on_device = false);
 void evaluate(gicp_ctx* c, const double* T, const gicp_params* p, const gicp_report_spec* spec, gicp_report* out);
 void align_trace(gicp_ctx* c, const double* T0, const gicp_params* p, double* T_out, gicp_result* res, gicp_trace* trace);
+
+// gicp_batch.cpp: batched registration
+void batch_align(gicp_ctx* c, int dim, const double* xyz, const int64_t* offsets, int n_clouds,
+                 const gicp_batch_problem* problems, int n_problems, const gicp_params& prm, double* T_out,
+                 gicp_batch_result* res, gicp_batch_debug* dbg);
 
 // gicp_exchange.cpp: the three statistics exchanges (RCCL, host hook, IPC peers); one per context
 void drop_comm(gicp_ctx* c);

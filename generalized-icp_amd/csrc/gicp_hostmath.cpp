@@ -764,6 +764,15 @@ int current_failure(std::string& msg) {
 namespace {
 thread_local std::string t_host_err;
 }
+namespace gicp {
+// the message of a call refused before it had a context to leave it in (gicp_batch_align's argument checks)
+void set_host_error(const std::string& msg) noexcept {
+    try {
+        t_host_err = msg;
+    } catch (...) {
+    }
+}
+}  // namespace gicp
 
 extern "C" {
 

@@ -129,5 +129,6 @@ void check_report_spec(const gicp_report_spec* spec, double dc);
 void check_cloud_args(const double* xyz, int64_t n, int dim);
 void check_shard(int shard, int nshards);
 int current_failure(std::string& msg);
+void set_host_error(const std::string& msg) noexcept;
 
 }  // namespace gicp

@@ -395,6 +395,46 @@ struct EvalArgs {
     unsigned long long* out;  // [kEvalOutWords]
 };
 
+// Batched registration (gicp_batch.hip): many small cloud pairs in one launch.  All clouds lie
+// concatenated in their input order (no index is built: the searches are brute force in LDS), cloud c the rows
+// offsets[c] .. offsets[c + 1].  All pointers device memory.
+constexpr int kBatchMaxPoints = 2048;   // largest cloud: its fp64 points, with the workgroup's fixed LDS, fit 64 KB
+constexpr int kBatchThreads = 256;
+constexpr int kBatchRows = 64;          // source rows per chunk of the statistics reduction
+struct BatchCovArgs {
+    const double* xyz;        // [rows][dim]
+    const int64_t* offsets;   // [n_clouds + 1]
+    const int2* work;         // [grid] (cloud, first query row within it): kBatchThreads query rows per workgroup
+    int32_t cap;              // LDS rows: the largest cloud of the batch
+    int32_t min_nb;
+    double dn2, eps_a, m_scale;   // as CovArgs
+    double4* cov;             // [rows] (a, m0, m1, m2): C = a I - m m^T
+    int32_t* count;           // [rows]
+    double* dbg_cov;          // [rows][dim][dim] (nullable)
+};
+// what a problem's workgroup leaves behind
+struct BatchOut {
+    double T[16];
+    double loss, mse;
+    int32_t iterations, converged, converged_at, stop_reason, solve_fail, pad;
+    double stats[80];         // the statistics its last solve consumed (IterState::stats_solved)
+};
+struct BatchArgs {
+    const double* xyz;
+    const int64_t* offsets;
+    const double4* cov;
+    const gicp_batch_problem* prob;   // [grid]
+    const int64_t* row0;      // [grid] first row of the problem in dbg_index / dbg_dist
+    int32_t cap;              // LDS rows of the target: the largest target of the batch
+    int32_t max_iter, fixed;
+    int32_t cov_model, robust_kernel;
+    double tol, trans_eps, rot_cos, fit_eps, rel_eps;   // as IterState
+    double dc2_max, pl_inv, robust_c, robust_c2;        // as CorrArgs
+    BatchOut* out;            // [grid]
+    int64_t* dbg_index;       // (nullable)
+    double* dbg_dist;         // (nullable)
+};
+
 constexpr int nstat(int D) {
     return (D * (D + 1) / 2) * (D * (D + 1) / 2) + (D * (D + 1) / 2) * D + (D * (D + 1) / 2) + D * D + D + 2;
 }

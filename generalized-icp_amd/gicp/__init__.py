@@ -23,7 +23,7 @@ from ._lib import Debug, Params, Report, ReportSpec, Result, Trace, check, dptr
 
 __all__ = ["gicp", "apply_transformation", "Engine", "RotatedCovariances", "expand_stats", "stats_size",
            "default_params", "last_result", "voxel_downsample", "filter_points", "filter_points_host", "deskew", "deskew_host", "motion_twist", "information",
-           "sym_eig"]
+           "sym_eig", "align_batch", "multistart", "batch_max_points", "pick_start"]
 
 
 def stats_size(dim):
@@ -580,6 +580,119 @@ class Engine:
             for k in ("top_src", "top_tgt", "top_det"):
                 out.pop(k)
         return Tout, r, out
+
+    def align_batch(self, clouds, pairs, T0=None, params=None, debug=False):
+        """Many small registrations in one launch (gicp_batch_align): `clouds` a list of N x 2 or
+        N x 3 arrays of one dimension, each of 1 .. batch_max_points(dim) rows; `pairs` a list of (source, target)
+        cloud numbers (a cloud may serve many pairs); T0 None (identity), one pose, or one per pair.  One
+        gicp_params serves the batch; the engine's clouds, caches, voxel and filter settings are neither used nor
+        changed.  Returns (T [B, d+1, d+1], results): per pair a dict of status (0, or GICP_E_INVALID = -1 when
+        its pose solve failed: it keeps the pose it had, the others are unaffected), iterations, converged,
+        converged_at, stop_reason (named as Engine.align names it), correspondences, final_loss, mse.  With
+        debug=True also a dict: per cloud 'covariances' and 'neighbor_counts', per pair 'index', 'distance'
+        (of the last pass it ran) and 'stats'.  A pair's outputs do not depend on what else is in the batch."""
+        cl = [self._cloud(c) for c in clouds]
+        if not cl:
+            raise ValueError("align_batch: clouds must not be empty")
+        d = cl[0].shape[1]
+        if any(c.shape[1] != d for c in cl):
+            raise ValueError("align_batch: all clouds must have one dimension")
+        pr = np.asarray(list(pairs), dtype=np.int64).reshape(-1, 2) if len(pairs) else np.empty((0, 2), np.int64)
+        B = len(pr)
+        if B < 1:
+            raise ValueError("align_batch: pairs must not be empty")
+        if T0 is None:
+            T0 = np.eye(d + 1)
+        T0 = np.asarray(T0, dtype=np.float64)
+        if T0.shape == (d + 1, d + 1):
+            T0 = np.broadcast_to(T0, (B, d + 1, d + 1))
+        if T0.shape != (B, d + 1, d + 1):
+            raise ValueError(f"align_batch: T0 must be None, one {d + 1} x {d + 1} pose or one per pair, got shape {T0.shape}")
+        if pr.min() < -2 ** 31 or pr.max() >= 2 ** 31:
+            raise ValueError("align_batch: a cloud number is out of range")
+        xyz = np.ascontiguousarray(np.concatenate(cl, axis=0))
+        off = np.zeros(len(cl) + 1, dtype=np.int64)
+        np.cumsum([len(c) for c in cl], out=off[1:])
+        probs = (_lib.BatchProblem * B)()
+        raw = np.frombuffer(probs, dtype=np.dtype([("source", np.int32), ("target", np.int32), ("T0", np.float64, 16)]))
+        raw["source"], raw["target"] = pr[:, 0], pr[:, 1]
+        raw["T0"][:] = 0.0
+        raw["T0"][:, :(d + 1) ** 2] = T0.reshape(B, -1)
+        Tout = np.empty((B, d + 1, d + 1))
+        res = (_lib.BatchResult * B)()
+        p = params or default_params(d)
+        dbg = out = None
+        if debug:
+            rows = int(off[-1])
+            ok = (pr >= 0).all() and (pr < len(cl)).all()     # (else the call is refused before it writes)
+            nsrc = np.array([len(cl[s]) for s in pr[:, 0]], dtype=np.int64) if ok else np.zeros(B, np.int64)
+            out = dict(cov=np.empty((rows, d, d)), cnt=np.empty(rows, dtype=np.int32),
+                       index=np.empty(max(1, int(nsrc.sum())), dtype=np.int64), distance=np.empty(max(1, int(nsrc.sum()))),
+                       stats=np.empty((B, _lib.MAX_STATS)))
+            dbg = _lib.BatchDebug(dptr(out["cov"]), out["cnt"].ctypes.data_as(C.POINTER(C.c_int32)),
+                                  out["index"].ctypes.data_as(C.POINTER(C.c_int64)), dptr(out["distance"]), dptr(out["stats"]))
+        check(self._lib.gicp_batch_align(self._ctx, d, dptr(xyz), off.ctypes.data_as(C.POINTER(C.c_int64)), len(cl), probs, B,
+                                         C.byref(p), dptr(Tout), res, C.byref(dbg) if dbg else None), self._ctx,
+              "gicp_batch_align")
+        results = []
+        for r in res:
+            e = {k: getattr(r, k) for k, _ in r._fields_ if k != "pad"}
+            e["stop_reason"] = _lib.STOP_REASONS.get(e["stop_reason"], e["stop_reason"])
+            results.append(e)
+        if not debug:
+            return Tout, results
+        ps = np.concatenate([[0], np.cumsum(nsrc)])
+        ns = stats_size(d)
+        return Tout, results, dict(
+            covariances=[out["cov"][off[c]:off[c + 1]] for c in range(len(cl))],
+            neighbor_counts=[out["cnt"][off[c]:off[c + 1]] for c in range(len(cl))],
+            index=[out["index"][ps[b]:ps[b + 1]] for b in range(B)],
+            distance=[out["distance"][ps[b]:ps[b + 1]] for b in range(B)],
+            stats=[out["stats"][b, :ns] for b in range(B)])
+
+
+def batch_max_points(dim):
+    """The largest cloud align_batch takes (gicp_batch_max_points)."""
+    n = _lib.load().gicp_batch_max_points(int(dim))
+    if n < 0:
+        raise ValueError("batch_max_points: dim must be 2 or 3")
+    return n
+
+
+def align_batch(clouds, pairs, T0=None, params=None, debug=False, device=0, **params_kw):
+    """Engine.align_batch on the process's engine of `device`; params_kw are gicp_params fields over the defaults
+    (or over `params`), e.g. max_distance_correspondence=20.0."""
+    cl = [Engine._cloud(c) for c in clouds]
+    if params_kw:
+        if not cl:
+            raise ValueError("align_batch: clouds must not be empty")
+        base = {k: getattr(params, k) for k, _ in Params._fields_} if params is not None else {}
+        base.update(params_kw)
+        params = default_params(cl[0].shape[1], **base)
+    return _engine(int(device)).align_batch(cl, pairs, T0, params, debug)
+
+
+def pick_start(results):
+    """multistart's choice among a list of result dicts: the start with the most correspondences among those
+    with status == 0, ties to the smaller mse, then to the lower index; None when every start failed."""
+    best = None
+    for i, r in enumerate(results):
+        if r["status"] != 0:
+            continue
+        key = (-int(r["correspondences"]), float(r["mse"]))
+        if best is None or key < best[0]:
+            best = (key, i)
+    return None if best is None else best[1]
+
+
+def multistart(source, target, T0s, **kw):
+    """One pair registered from len(T0s) start poses in one launch (a multi-start search over yaw when odometry
+    is lost): returns (best, T [B, d+1, d+1], results) with `best` = pick_start(results).  kw as align_batch's."""
+    T0s = np.asarray(T0s, dtype=np.float64)
+    if T0s.ndim != 3 or len(T0s) < 1:
+        raise ValueError(f"multistart: T0s must be B >= 1 poses [B, d+1, d+1], got shape {T0s.shape}")
+    T, results = align_batch([source, target], [(0, 1)] * len(T0s), T0s, **kw)[:2]
+    return pick_start(results), T, results
 
 
 def _report_spec(thresholds, quantiles):

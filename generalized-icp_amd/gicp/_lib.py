@@ -130,6 +130,42 @@ class Filter(C.Structure):
     ]
 
 
+class BatchProblem(C.Structure):
+    """gicp_batch_problem (include/gicp_hip.h): one registration of a batch."""
+    _fields_ = [
+        ("source", C.c_int32),
+        ("target", C.c_int32),
+        ("T0", C.c_double * 16),
+    ]
+
+
+class BatchResult(C.Structure):
+    """gicp_batch_result: a problem's outcome; status 0, or GICP_E_INVALID when its pose solve failed."""
+    _fields_ = [
+        ("status", C.c_int32),
+        ("iterations", C.c_int32),
+        ("converged", C.c_int32),
+        ("converged_at", C.c_int32),
+        ("stop_reason", C.c_int32),
+        ("pad", C.c_int32),
+        ("correspondences", C.c_int64),
+        ("final_loss", C.c_double),
+        ("mse", C.c_double),
+    ]
+
+
+class BatchDebug(C.Structure):
+    """gicp_batch_debug: optional caller-allocated outputs of gicp_batch_align."""
+    _fields_ = [
+        ("covariances", C.POINTER(C.c_double)),
+        ("neighbor_counts", C.POINTER(C.c_int32)),
+        ("index", C.POINTER(C.c_int64)),
+        ("distance", C.POINTER(C.c_double)),
+        ("stats", C.POINTER(C.c_double)),
+    ]
+
+
+MAX_STATS = 74
 REPORT_MAX = 8
 
 
@@ -236,6 +272,9 @@ SIGNATURES = {
     "gicp_evaluate": (C.c_int, [_VP, _DP, C.POINTER(Params), C.POINTER(ReportSpec), C.POINTER(Report)]),
     "gicp_information": (C.c_int, [C.c_int, _DP, _DP, _DP, _DP]),
     "gicp_sym_eig": (C.c_int, [C.c_int, _DP, _DP, _DP]),
+    "gicp_batch_max_points": (C.c_int, [C.c_int]),
+    "gicp_batch_align": (C.c_int, [_VP, C.c_int, _DP, C.POINTER(C.c_int64), C.c_int, C.POINTER(BatchProblem), C.c_int,
+                                   C.POINTER(Params), _DP, C.POINTER(BatchResult), C.POINTER(BatchDebug)]),
 }
 
 # gicp_allreduce_fn: int (*)(double* buf, int n, void* user)
@@ -246,8 +285,9 @@ _lib = None
 # the sources gicp_build_info()'s hash covers, in the Makefile's HASH_SRCS order
 HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
              "csrc/gicp_build.cpp", "csrc/gicp_align.cpp", "csrc/gicp_exchange.cpp", "csrc/gicp_voxel.hip",
-             "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_filter.hip", "csrc/gicp_internal.h", "csrc/gicp_mem.h",
-             "csrc/gicp_sweep.h", "csrc/gicp_filter.h", "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
+             "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_filter.hip", "csrc/gicp_batch.hip", "csrc/gicp_batch.cpp",
+             "csrc/gicp_internal.h", "csrc/gicp_mem.h",
+             "csrc/gicp_sweep.h", "csrc/gicp_filter.h", "csrc/gicp_cov_dev.h", "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
              "../include/gicp_hip.h")
 
 

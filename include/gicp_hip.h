@@ -160,7 +160,8 @@ int gicp_version(void);                          /* 100 * major + minor; 101: gi
                                                     compensation (gicp_sweep, gicp_deskew, gicp_*_sweep); 103: the
                                                     registration report (gicp_evaluate, gicp_information,
                                                     gicp_sym_eig); 104: the input filters (gicp_filter,
-                                                    gicp_filter_points[_host], gicp_set_filter) */
+                                                    gicp_filter_points[_host], gicp_set_filter); 105: batched
+                                                    registration (gicp_batch_align, gicp_batch_max_points) */
 int gicp_stats_size(int dim);                    /* 26 (dim 2) or 74 (dim 3) */
 void gicp_default_params(int dim, gicp_params* out);
 const char* gicp_strerror(int code);
@@ -206,8 +207,9 @@ int gicp_peer_close(gicp_ctx* ctx);   /* back to no exchange (RCCL / hook as set
 /* Build provenance of this library: "src=<first 16 hex of sha256 over the sources>;git=<rev>;built=<date
  * time>;arch=gfx950".  The source hash covers csrc/{gicp_kernels.hip, gicp_capi.cpp, gicp_solver.cpp,
  * gicp_cg.cpp, gicp_hostmath.cpp, gicp_build.cpp, gicp_align.cpp, gicp_exchange.cpp, gicp_voxel.hip, gicp_sweep.hip,
- * gicp_eval.hip, gicp_filter.hip, gicp_internal.h, gicp_mem.h, gicp_sweep.h, gicp_filter.h, gicp_solver.h,
- * gicp_solve_dev.h, gicp_hostmath.h, gicp_host.h} and include/gicp_hip.h, concatenated in that order, so
+ * gicp_eval.hip, gicp_filter.hip, gicp_batch.hip, gicp_batch.cpp, gicp_internal.h, gicp_mem.h, gicp_sweep.h,
+ * gicp_filter.h, gicp_cov_dev.h, gicp_solver.h, gicp_solve_dev.h, gicp_hostmath.h, gicp_host.h} and
+ * include/gicp_hip.h, concatenated in that order, so
  * a caller can prove the loaded library was compiled from the sources beside it. */
 const char* gicp_build_info(void);
 
@@ -492,7 +494,7 @@ int gicp_filter_points(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, con
                        int64_t* out_index, int32_t* out_count, int64_t* M_out);
 int gicp_filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz,
                             int64_t* out_index, int32_t* out_count, int64_t* M_out);
-const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host ("" if none) */
+const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host or refused gicp_batch_align ("" if none) */
 int gicp_set_filter(gicp_ctx* ctx, const gicp_filter* f);
 
 /* ---- local voxel map ----------------------------------------------------------------
@@ -605,6 +607,66 @@ int gicp_information(int dim, const double* stats, const double* T, double* H, d
 /* A [n][n] row-major, 1 <= n <= 6 (only (A + A^T) / 2 is used) -> w[n] ascending, V[n][n] with column k the
  * unit eigenvector of w[k].  GICP_E_INVALID for n out of range, a NULL pointer or a non-finite entry. */
 int gicp_sym_eig(int n, const double* A, double* w_ascending, double* V_columns_row_major);
+
+/* ---- batched registration: many small cloud pairs in one launch ----
+ * A particle filter, a multi-start search over yaw, a fleet, loop-closure candidates: hundreds of registrations
+ * of clouds of a few hundred points each.  One such pair keeps a few wavefronts busy and a gicp_align call is
+ * launch and synchronisation latency; gicp_batch_align runs ONE workgroup per problem, persistent over the
+ * problem's whole outer loop (nearest neighbours by exact fp64 brute force over the target held in LDS, the
+ * statistics reduced in a fixed order, the pose solve and the stopping rules of gicp_align on the device), so a
+ * batch costs two launches and one synchronisation however many problems it holds.
+ *
+ * Clouds: `xyz` holds all clouds concatenated, [offsets[n_clouds]][dim]; cloud c is rows offsets[c] ..
+ * offsets[c + 1] (offsets[0] = 0), of 1 .. gicp_batch_max_points(dim) points.  Many problems may name the same
+ * cloud: a multi-start search is one pair with n_problems different T0.  One gicp_params serves the whole batch
+ * (NULL: the defaults of `dim`); k_neighbors, max_distance_nearest_neighbors, epsilon, ratio and min_neighbors give
+ * the surface covariances of every cloud (computed once per cloud, the semantics of gicp_set_target's), the rest
+ * is gicp_align's.  The context's voxel and filter settings (gicp_set_voxel, gicp_set_filter) do NOT apply to
+ * batch clouds: they are registered as given.
+ *
+ * A problem's outputs depend on its two clouds, its T0 and the parameters alone: the same bits whatever else is
+ * in the batch, at any position, batch size, call history or context.  Correspondences are exact: the nearest
+ * target by d2 = ((dx*dx + dy*dy) + dz*dz), every operation rounded on its own, equal distances to the lower
+ * row, accepted iff sqrt(d2) <= max_distance_correspondence.
+ *
+ * GICP_E_INVALID, before anything runs, with the outputs untouched and a message that names the cloud or
+ * problem (gicp_last_error, and gicp_last_host_error for this thread): a dim other than 2 or 3; n_clouds < 1 or
+ * n_problems < 1; a NULL xyz, offsets, problems or T_out; offsets that do not start at 0 or do not ascend; an
+ * empty or oversized cloud; a cloud number out of range; non-finite points or T0; the parameter errors
+ * gicp_align and gicp_set_target refuse (cov_model, robust kernel and scale, k_neighbors).  These checks come
+ * before the context is looked at, so they need no GPU; a NULL context is GICP_E_INVALID after them.
+ * A problem whose pose solve fails, or whose last pass accepted no correspondence, does not fail the call: it
+ * reports status GICP_E_INVALID, keeps the pose it had (T0 when its first solve failed), and the others are
+ * unaffected.  A GICP_ROBUST_TUKEY pass that gives every
+ * correspondence weight 0 is no failure (gicp_align's rule).
+ *
+ * The call runs on the context's stream and leaves the context's clouds, voxel map, caches, settings and
+ * statistics exchange exactly as they were; its device buffers are the context's own (grow-only). */
+typedef struct gicp_batch_problem {
+    int32_t source, target;    /* cloud numbers */
+    double T0[16];             /* the start pose, (dim+1)^2 row-major in the first entries */
+} gicp_batch_problem;
+typedef struct gicp_batch_result {
+    int32_t status;            /* GICP_OK, or GICP_E_INVALID: this problem's pose solve failed (degenerate
+                                  statistics, e.g. no correspondence) */
+    int32_t iterations, converged, converged_at, stop_reason, pad;   /* as gicp_result */
+    int64_t correspondences;
+    double final_loss, mse;    /* as gicp_result */
+} gicp_batch_result;
+typedef struct gicp_batch_debug {        /* all optional, caller-allocated */
+    double* covariances;       /* [rows of all clouds][dim][dim], cloud after cloud, input order */
+    int32_t* neighbor_counts;  /* [rows of all clouds] */
+    int64_t* index;            /* per problem, its source's rows: target row within its target cloud, -1 rejected;
+                                  problem b starts at the sum of the source sizes of problems < b */
+    double* distance;          /* same layout: distance to the nearest target row (accepted or not) */
+    double* stats;             /* [n_problems][GICP_MAX_STATS], the first gicp_stats_size(dim) used: the last pass
+                                  each problem ran */
+} gicp_batch_debug;
+int gicp_batch_max_points(int dim);   /* largest cloud a batch takes (2048); GICP_E_INVALID for a dim other than 2, 3 */
+int gicp_batch_align(gicp_ctx* ctx, int dim, const double* xyz, const int64_t* offsets, int n_clouds,
+                     const gicp_batch_problem* problems, int n_problems, const gicp_params* p,
+                     double* T_out /* [n_problems][(dim+1)^2] */, gicp_batch_result* res /* [n_problems], may be NULL */,
+                     gicp_batch_debug* dbg /* may be NULL */);
 
 #ifdef __cplusplus
 }

@@ -21,96 +21,11 @@
 #include "gicp_internal.h"
 #include "gicp_solver.h"
 #include "gicp_solve_dev.h"
+#include "gicp_stats_dev.h"
+#include "gicp_wave_dev.h"
 
 namespace gicp {
 namespace {
-
-// dist2_exact's expression (gicp_kernels.hip): summed in axis order, every operation rounded on its own
-template <int D>
-__device__ __forceinline__ double batch_d2(const double (&a)[D], const double (&b)[D]) {
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double d = __dsub_rn(a[k], b[k]);
-        s = __dadd_rn(s, __dmul_rn(d, d));
-    }
-    return s;
-}
-
-// smallest_eigvec3 (gicp_cov_dev.h) with the eigenvector picked by selects: that function ends on V[k][m] with
-// m found at run time, which puts its V into a scratch frame (k_knn_cov carries one; these kernels must not).
-// The same sweeps in the same order, so the same bits.
-__device__ __forceinline__ void batch_eigvec3(double A[3][3], double* n) {
-    double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 12; ++sweep) {
-        const double off = fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]);
-        if (off == 0.0) break;
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = pq == 2 ? 1 : 0;
-            const int qq = pq == 0 ? 1 : 2;
-            const double apq = A[p][qq];
-            if (apq == 0.0) continue;
-            const double theta = (A[qq][qq] - A[p][p]) / (2.0 * apq);
-            const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {  // A <- J^T A J
-                const double akp = A[k][p], akq = A[k][qq];
-                A[k][p] = c * akp - s * akq;
-                A[k][qq] = s * akp + c * akq;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double apk = A[p][k], aqk = A[qq][k];
-                A[p][k] = c * apk - s * aqk;
-                A[qq][k] = s * apk + c * aqk;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double vkp = V[k][p], vkq = V[k][qq];
-                V[k][p] = c * vkp - s * vkq;
-                V[k][qq] = s * vkp + c * vkq;
-            }
-        }
-    }
-    // m = 0; if (A[1][1] < A[m][m]) m = 1; if (A[2][2] < A[m][m]) m = 2
-    const bool m1 = A[1][1] < A[0][0];
-    const double am = m1 ? A[1][1] : A[0][0];
-    const bool m2 = A[2][2] < am;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) n[k] = m2 ? V[k][2] : (m1 ? V[k][1] : V[k][0]);
-}
-
-// cov_descriptor (gicp_cov_dev.h), its 3-D branch on batch_eigvec3
-template <int D>
-__device__ __forceinline__ double4 batch_cov_descriptor(const CovSums<D>& A, int min_nb, double eps_a, double m_scale) {
-    if constexpr (D == 2) {
-        return cov_descriptor<2>(A, min_nb, eps_a, m_scale);
-    } else {
-        double4 out;
-        out.x = 1.0;
-        out.y = out.z = out.w = 0.0;
-        if (A.n < (double)min_nb) return out;
-        const double n = A.n;
-        double M[3][3];
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = a; b < 3; ++b) {
-                M[a][b] = M[b][a] = (A.ss[k] - A.s[a] * A.s[b] / n) / (n - 1.0);
-                ++k;
-            }
-        double nv[3];
-        batch_eigvec3(M, nv);
-        out.x = eps_a;
-        out.y = nv[0] * m_scale;
-        out.z = nv[1] * m_scale;
-        out.w = nv[2] * m_scale;
-        return out;
-    }
-}
 
 constexpr int kBatchUnroll = 4;   // target rows a lane has in flight in k_batch_align's search
 
@@ -140,7 +55,7 @@ __global__ void __launch_bounds__(kBatchThreads) k_batch_cov(BatchCovArgs A) {
         double q[D];
 #pragma unroll
         for (int a = 0; a < D; ++a) q[a] = s_mem[a * cap + j];
-        const double d2 = batch_d2<D>(q, p);
+        const double d2 = dist2_exact<D>(q, p);
         if (d2 < lk[K - 1]) {
 #pragma unroll
             for (int m = K - 1; m > 0; --m) lk[m] = fmin(lk[m], fmax(lk[m - 1], d2));
@@ -169,7 +84,7 @@ __global__ void __launch_bounds__(kBatchThreads) k_batch_cov(BatchCovArgs A) {
         double q[D];
 #pragma unroll
         for (int a = 0; a < D; ++a) q[a] = s_mem[a * cap + j];
-        const double d2 = batch_d2<D>(q, p);
+        const double d2 = dist2_exact<D>(q, p);
         const bool take = c > 0 && (d2 < tau || (d2 == tau && eq_left > 0));
         if (take) {
             if (d2 == tau) --eq_left;
@@ -179,7 +94,7 @@ __global__ void __launch_bounds__(kBatchThreads) k_batch_cov(BatchCovArgs A) {
             cov_add<D>(S, d);
         }
     }
-    const double4 cv = batch_cov_descriptor<D>(S, A.min_nb, A.eps_a, A.m_scale);
+    const double4 cv = cov_descriptor<D, true>(S, A.min_nb, A.eps_a, A.m_scale);
     A.cov[o + i] = cv;
     A.count[o + i] = (int)S.n;
     if (A.dbg_cov) {   // C = a I - m m^T, the products rounded on their own (k_rotate_cov's formula at R = I)
@@ -212,38 +127,6 @@ struct BatchLds {
 static_assert(sizeof(IterState) % 8 == 0 && nstat_ext(3) <= 80, "the state and the statistics are whole doubles");
 static_assert(BatchLds<3>::bytes(kBatchMaxPoints) <= 65536 && BatchLds<2>::bytes(kBatchMaxPoints) <= 65536,
               "the largest target fits a workgroup's 64 KB");
-
-// which u and v term statistic k is the product of (A[ab][ij], B[ab][i], C[ab], gR[a][i], gt[a], c0,
-// count; k = nstat(D): the sum of |r|^2)
-template <int D>
-__device__ __forceinline__ void stat_terms(int k, int& iu, int& iv) {
-    constexpr int NS = D * (D + 1) / 2;
-    iv = NS + D;   // the 1
-    if (k < NS * NS) {
-        iu = k / NS;
-        iv = k % NS;
-        return;
-    }
-    k -= NS * NS;
-    if (k < NS * D) {
-        iu = k / D;
-        iv = NS + k % D;
-        return;
-    }
-    k -= NS * D;
-    if (k < NS) {
-        iu = k;
-        return;
-    }
-    k -= NS;
-    if (k < D * D) {
-        iu = NS + k / D;
-        iv = NS + k % D;
-        return;
-    }
-    k -= D * D;
-    iu = NS + k;   // gt[a], then c0, the count, the sum of |r|^2
-}
 
 template <int D, bool Robust>
 __global__ void __launch_bounds__(kBatchThreads) k_batch_align(BatchArgs A) {
@@ -331,7 +214,7 @@ __global__ void __launch_bounds__(kBatchThreads) k_batch_align(BatchArgs A) {
                         double q[D];
 #pragma unroll
                         for (int a = 0; a < D; ++a) q[a] = s_tgt[a * cap + jc];
-                        const double d2 = batch_d2<D>(q, pp);
+                        const double d2 = dist2_exact<D>(q, pp);
                         d2u[k] = j < nt ? d2 : INFINITY;
                     }
 #pragma unroll
@@ -350,7 +233,8 @@ __global__ void __launch_bounds__(kBatchThreads) k_batch_align(BatchArgs A) {
                     bj = oj;
                 }
             }
-            // ---- W = inv(R C_s R^T + C_t) or its model, the robust weight, r: k_corr's epilogue restated ----
+            // ---- W = inv(R C_s R^T + C_t) or its model, the robust weight, r: k_corr's epilogue restated (no shared
+            // form left both kernels' code as it is) ----
             double u[NU] = {}, v[NV] = {};
             const bool writer = valid && pl == 0;
             if (writer) {

@@ -1,1131 +1,27 @@
-// gicp_kernels.hip — the MI355X (gfx950) hot path of GICP.
+// gicp_corr.hip — the per-iteration pass of GICP on the MI355X (gfx950), and the solve that follows it.
 //
 // Reference behaviour (python-implementation/gicp.py):
-//   k_knn_cov   <- compute_covariance_matrix / _single_point, gicp.py:5-35
-//                  (k nearest incl. self, distance strictly < d_n, np.cov, eig ->
-//                  surface-aligned covariance; identity for isolated points)
 //   k_corr      <- the per-iteration correspondence + weight loop, gicp.py:119-145
 //                  (exact 1-NN in the target, accept d <= d_c, W = inv(C_s + C_t)),
 //                  fused with the sufficient statistics of loss()/grad_loss()
 //                  (gicp.py:52-76) so the inner minimisation needs no further pass
 //   k_solve     <- the inner solve + convergence test on the device (gicp.py:148-167)
+//   k_peer_probe   no counterpart: the self-test of the in-kernel exchange between ranks
 //
-// Design: one wave = one query tile of <= 64 Morton-coherent points.
-// Database tiles are culled with a three-level AABB hierarchy (super-blocks of 64 blocks of 64 tiles, tested
-// one per lane, ballot), staged through LDS as fp32 SoA and scanned with a
-// broadcast read; lanes keep packed (d2 | row) keys.  The fp32 screen carries an
-// explicit error bound: a lane whose winner is within that bound of a rival (or of
-// the d_n / d_c cut) is re-resolved exactly in fp64, so indices match an fp64
-// KD-tree exactly.  No MFMA: there is no dense contraction in this path.
+// k_corr, k_peer_probe and k_solve share this translation unit on purpose: peer_exchange and its LDS word are
+// laid out per set of kernels that reach them (see the comment on peer_exchange).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <utility>
 
-#include "gicp_cov_dev.h"
 #include "gicp_internal.h"
-#include "gicp_solver.h"
+#include "gicp_search_dev.h"
 #include "gicp_solve_dev.h"
+#include "gicp_solver.h"
+#include "gicp_stats_dev.h"
+#include "gicp_wave_dev.h"
 
 namespace gicp {
-
-// ---------------------------------------------------------------------------
-// helpers
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int lane_id() { return __lane_id(); }
-__device__ __forceinline__ unsigned umed3(unsigned a, unsigned b, unsigned c) {
-    return max(min(a, b), min(max(a, b), c));
-}
-__device__ __forceinline__ float key_d2(unsigned k) { return __uint_as_float(k & ~63u); }
-// margin of the fp32 screen at d2 (raw v_sqrt_f32, inflated past its 1-ulp error: the bound stays conservative)
-__device__ __forceinline__ float marg(const Margin& m, float d2) {
-    return fmaf(m.a * 1.0001f, __builtin_amdgcn_sqrtf(d2), fmaf(m.c, d2, m.b));
-}
-
-// Wave-wide min / max of floats that are >= 0 or a negative "none" marker, result uniform
-// (SGPR): signed-integer compares on the bit patterns (monotonic for such values, no NaN
-// canonicalisation), each step one v_{min,max}_i32 with a DPP source: row_shr 1/2/4/8,
-// row_bcast 15/31, then readlane 63.
-#define GICP_WAVE_REDUCE(OP, ID, x)                                                      \
-    x = OP(x, __builtin_amdgcn_update_dpp(ID, x, 0x111, 0xf, 0xf, false));               \
-    x = OP(x, __builtin_amdgcn_update_dpp(ID, x, 0x112, 0xf, 0xf, false));               \
-    x = OP(x, __builtin_amdgcn_update_dpp(ID, x, 0x114, 0xf, 0xf, false));               \
-    x = OP(x, __builtin_amdgcn_update_dpp(ID, x, 0x118, 0xf, 0xf, false));               \
-    x = OP(x, __builtin_amdgcn_update_dpp(ID, x, 0x142, 0xa, 0xf, false));               \
-    x = OP(x, __builtin_amdgcn_update_dpp(ID, x, 0x143, 0xc, 0xf, false));
-__device__ __forceinline__ float wave_minf(float v) {
-    int x = __float_as_int(v);
-    GICP_WAVE_REDUCE(min, 0x7fffffff, x)
-    return __int_as_float(__builtin_amdgcn_readlane(x, 63));
-}
-__device__ __forceinline__ float wave_maxf(float v) {
-    int x = __float_as_int(v);
-    GICP_WAVE_REDUCE(max, (int)0x80000000, x)
-    return __int_as_float(__builtin_amdgcn_readlane(x, 63));
-}
-__device__ __forceinline__ float readlane_f(float v, int k) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k));
-}
-__device__ __forceinline__ double readlane_d(double v, int k) {
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), k);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), k);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-// wave minimum of keys < 2^31 (screen keys: non-negative fp32 bits), uniform
-__device__ __forceinline__ unsigned wave_min_key(unsigned v) {
-    int x = (int)v;
-    GICP_WAVE_REDUCE(min, 0x7fffffff, x)
-    return (unsigned)__builtin_amdgcn_readlane(x, 63);
-}
-__device__ __forceinline__ double wave_mind(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ double wave_maxd(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ void wave_sync() { __builtin_amdgcn_wave_barrier(); }
-// ascending bitonic sort of one (key, val) pair per lane across the wave; ties by val (deterministic)
-__device__ __forceinline__ void wave_sort64(float& key, int& val) {
-    const int l = __lane_id();
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1)
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const float pk = __shfl_xor(key, j);
-            const int pv = __shfl_xor(val, j);
-            const bool take_min = ((l & k) == 0) == ((l & j) == 0);
-            const bool less = pk < key || (pk == key && pv < val);
-            const bool greater = pk > key || (pk == key && pv > val);
-            if (take_min ? less : greater) {
-                key = pk;
-                val = pv;
-            }
-        }
-}
-// any lane: the ballot's scalar result tested directly (no bool -> int -> compare round trip)
-__device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0; }
-
-// Diagnostic-only phase timer (build with `make STAMPS=1`): s_memtime cycles per phase per wave.
-// 0 setup, 1 traversal tests, 2 tile need-test + staging, 3 row scan, 4 fp64 fallback,
-// 5 epilogue (W, statistics), 6 statistics reduction.  Compiles to nothing otherwise.
-struct Stamps {
-#ifdef GICP_STAMPS
-    unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long last = 0, rt0 = 0;
-    __device__ __forceinline__ void start() {
-        last = __builtin_amdgcn_s_memtime();
-        rt0 = __builtin_amdgcn_s_memrealtime();
-    }
-    __device__ __forceinline__ void mark(int c) {
-        const unsigned long long t = __builtin_amdgcn_s_memtime();
-        acc[c] += t - last;
-        last = t;
-    }
-    // event counters: 0 tile visits, 1 tiles scanned, 2 chunks scanned, 3 list used, 4 list length,
-    // 5 traversal block tests, 6 traversal candidate blocks, 7 fp64 fallback tiles
-    unsigned cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    __device__ __forceinline__ void count(int k, unsigned v = 1) { cnt[k] += v; }
-#elif defined(GICP_TIMELINE)   // `make VARIANT=tl VDEFS=-DGICP_TIMELINE`: wave start/end, phase ends, counters
-    unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // realtime (100 MHz) at the end of the certificate + descent phase and at the end of the walk; the walk's
-    // kind (0 none, 1 candidate list, 2 list then full walk, 3 full walk, 4 sparse search); lanes that descended / walked
-    unsigned long long tdesc = 0, twalk = 0, ta = 0, tb = 0, te = 0, tf = 0;
-    unsigned kind = 0, ndesc = 0, nwalk = 0, nwalk_jp = 0;
-    float wb0 = 0.f;
-    __device__ __forceinline__ void start() {}
-    __device__ __forceinline__ void mark(int) {}
-    __device__ __forceinline__ void count(int k, unsigned v = 1) { cnt[k] += v; }
-#else
-    __device__ __forceinline__ void start() {}
-    __device__ __forceinline__ void mark(int) {}
-    __device__ __forceinline__ void count(int, unsigned = 1) {}
-#endif
-};
-
-#ifdef GICP_TIMELINE
-// realtime stamp taken once `a` and `b` are available (their loads complete): the asm's inputs make the
-// compiler wait for them first, and volatile asms keep their order
-template <class A, class B>
-__device__ __forceinline__ unsigned long long tl_after(A a, B b) {
-    unsigned long long t;
-    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "v"(a), "v"(b) : "memory");
-    return t;
-}
-#endif
-
-// exact-rounding fp64 square distance, summed in axis order without FMA contraction
-// (the order a KD-tree accumulates it in)
-template <int D>
-__device__ __forceinline__ double dist2_exact(const double* a, const double* b) {
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-        const double d = __dsub_rn(a[k], b[k]);
-        s = __dadd_rn(s, __dmul_rn(d, d));
-    }
-    return s;
-}
-
-__device__ __forceinline__ uint32_t spread2(uint32_t x) {
-    x &= 0xFFFFu;
-    x = (x | (x << 8)) & 0x00FF00FFu;
-    x = (x | (x << 4)) & 0x0F0F0F0Fu;
-    x = (x | (x << 2)) & 0x33333333u;
-    x = (x | (x << 1)) & 0x55555555u;
-    return x;
-}
-__device__ __forceinline__ uint32_t spread3(uint32_t x) {
-    x &= 0x3FFu;
-    x = (x | (x << 16)) & 0x030000FFu;
-    x = (x | (x << 8)) & 0x0300F00Fu;
-    x = (x | (x << 4)) & 0x030C30C3u;
-    x = (x | (x << 2)) & 0x09249249u;
-    return x;
-}
-__device__ __forceinline__ uint32_t morton_code(const double* p, int dim, const double* lo, double scale, int bits) {
-    const double maxc = (double)((1u << bits) - 1u);
-    uint32_t q[3] = {0, 0, 0};
-    for (int a = 0; a < dim; ++a) {
-        double v = (p[a] - lo[a]) * scale;
-        v = fmin(fmax(v, 0.0), maxc);
-        q[a] = (uint32_t)v;
-    }
-    return dim == 3 ? (spread3(q[0]) | (spread3(q[1]) << 1) | (spread3(q[2]) << 2))
-                    : (spread2(q[0]) | (spread2(q[1]) << 1));
-}
-
-// ---------------------------------------------------------------------------
-// index build
-// ---------------------------------------------------------------------------
-__global__ void k_morton(const double* __restrict__ xyz, int64_t n, int dim, DevCloud fr, uint32_t* codes,
-                         int32_t* idx) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double p[3] = {0, 0, 0};
-    for (int a = 0; a < dim; ++a) p[a] = xyz[i * dim + a];
-    codes[i] = morton_code(p, dim, fr.lo, fr.scale, fr.bits);
-    idx[i] = (int32_t)i;
-}
-
-// One wave per tile: gather the tile's points (original order -> sorted), fp64 AABB,
-// centre, fp32 relative coordinates, half-extents and radius.
-// Order of the rows inside a tile: a recursive median split instead of the Morton order the tile
-// was cut from.  Rows 0-31 / 32-63 are the halves along the tile's longest axis, each half is split
-// along its own longest axis, and so on down to the sub-tile size, so the sub-tiles are compact
-// boxes (a Morton run can straddle a cell boundary and span the whole tile).  Rows carry no meaning beyond the
-// sub-tile boxes (ties are resolved on original indices), so only the culling changes.
-__device__ __forceinline__ void split_order(double (&p)[3], int& o, int dim, bool v) {
-    const int l = lane_id();
-    const int cnt = __popcll(__ballot(v));   // valid rows are lanes 0 .. cnt-1, and stay there
-    const bool vv = l < cnt;
-    // each level halves every segment of `seg` rows along that segment's own longest axis
-    for (int seg = kTile; seg > kSubRows; seg >>= 1) {
-        double mn[3], mx[3];
-        for (int a = 0; a < 3; ++a) {
-            mn[a] = vv ? p[a] : 1e300;
-            mx[a] = vv ? p[a] : -1e300;
-            for (int s = 1; s < seg; s <<= 1) {   // xor offsets below seg stay inside the segment
-                mn[a] = fmin(mn[a], __shfl_xor(mn[a], s));
-                mx[a] = fmax(mx[a], __shfl_xor(mx[a], s));
-            }
-        }
-        int ax = 0;
-        for (int a = 1; a < dim; ++a)
-            if (mx[a] - mn[a] > mx[ax] - mn[ax]) ax = a;
-        const double span = mx[ax] - mn[ax];
-        const float t = span > 0.0 ? (float)((p[ax] - mn[ax]) / span) : 0.f;
-        float key = vv ? (float)(2 * (l / seg)) + t : 3e38f;   // segment s keeps keys in [2s, 2s + 1]
-        int src = l;
-        wave_sort64(key, src);
-        for (int a = 0; a < 3; ++a) p[a] = __shfl(p[a], src);
-        o = __shfl(o, src);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_build_tiles(const double* __restrict__ xyz_in, int dim,
-                                                      int32_t* __restrict__ perm, TileInfo* tiles, TileBox* boxes,
-                                                      int ntiles, double* xyz64, float4* rel32, int32_t* inv,
-                                                      unsigned* rho_bits) {
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const int T = blockIdx.x * kWavesPerWG + w;
-    if (T >= ntiles) return;
-    const int start = tiles[T].start, count = tiles[T].count;
-    const bool v = l < count;
-    const int i = start + l;
-    double p[3] = {0, 0, 0};
-    int o = 0;
-    if (v) {
-        o = perm[i];
-        for (int a = 0; a < dim; ++a) p[a] = xyz_in[(int64_t)o * dim + a];
-    }
-    split_order(p, o, dim, v);   // valid rows stay in lanes 0 .. count-1
-    if (v) {
-        perm[i] = o;
-        inv[o] = i;
-        double4 q;
-        q.x = p[0];
-        q.y = p[1];
-        q.z = p[2];
-        q.w = 0.0;
-        reinterpret_cast<double4*>(xyz64)[i] = q;
-    }
-    double c[3];
-    for (int a = 0; a < 3; ++a) {
-        const double mn = wave_mind(v ? p[a] : 1e300);
-        const double mx = wave_maxd(v ? p[a] : -1e300);
-        c[a] = a < dim ? 0.5 * (mn + mx) : 0.0;
-    }
-    float r[3];
-    for (int a = 0; a < 3; ++a) r[a] = v ? (float)(p[a] - c[a]) : 0.0f;
-    if (v) rel32[i] = make_float4(r[0], r[1], r[2], 0.0f);
-    float h[3];
-    for (int a = 0; a < 3; ++a) h[a] = wave_maxf(fabsf(r[a]));
-    const float rad = wave_maxf(sqrtf(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]));
-    // sub-tile boxes (min/max over each kSubRows-lane segment of the wave)
-    float smn[3], smx[3];
-    for (int a = 0; a < 3; ++a) {
-        smn[a] = v ? r[a] : 3e38f;
-        smx[a] = v ? r[a] : -3e38f;
-        for (int o = 1; o < kSubRows; o <<= 1) {
-            smn[a] = fminf(smn[a], __shfl_xor(smn[a], o));
-            smx[a] = fmaxf(smx[a], __shfl_xor(smx[a], o));
-        }
-    }
-    if (l % kSubRows == 0) {
-        const int g = l / kSubRows;
-        TileInfo& t = tiles[T];
-        for (int a = 0; a < 3; ++a) {
-            const bool empty = smn[a] > smx[a];
-            const float cc = empty ? 0.f : 0.5f * (smn[a] + smx[a]);
-            // half-extent rounded up so the box covers both extremes exactly
-            const float hh = empty ? -1e30f : fmaxf(smx[a] - cc, cc - smn[a]) * (1.0f + 2.4e-7f);
-            t.sc[a][g] = cc;
-            t.sh[a][g] = hh;
-        }
-    }
-    if (l == 0) {
-        TileInfo& t = tiles[T];
-        for (int a = 0; a < 3; ++a) {
-            t.c[a] = c[a];
-            t.h[a] = h[a];
-        }
-        t.radius = rad;
-        TileBox& b = boxes[T];
-        for (int a = 0; a < 3; ++a) {
-            b.c[a] = c[a];
-            b.h[a] = h[a];
-        }
-        b.start = start;
-        b.count = count;
-        b.pad = 0;
-        atomicMax(rho_bits, __float_as_uint(rad));
-    }
-}
-
-// One wave per block of 64 tiles: fp64 AABB over the tiles' boxes.
-// One level of the box hierarchy: box B covers children [64 B, 64 B + 64) of the level below
-// (tiles -> blocks; blocks -> super-blocks, stored after the blocks in the same array).
-template <class Child>
-__global__ void __launch_bounds__(256) k_build_blocks(const Child* __restrict__ kids, int nkids, BlockInfo* blocks,
-                                                       int nblocks, int dim) {
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    const int B = blockIdx.x * kWavesPerWG + w;
-    if (B >= nblocks) return;
-    const int t = B * kBlockTiles + l;
-    const bool v = t < nkids;
-    double lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = v ? kids[t].c[a] - (double)kids[t].h[a] : 1e300;
-        hi[a] = v ? kids[t].c[a] + (double)kids[t].h[a] : -1e300;
-        lo[a] = wave_mind(lo[a]);
-        hi[a] = wave_maxd(hi[a]);
-    }
-    if (l == 0) {
-        BlockInfo& b = blocks[B];
-        for (int a = 0; a < 3; ++a) {
-            const double c = a < dim ? 0.5 * (lo[a] + hi[a]) : 0.0;
-            const double hh = a < dim ? 0.5 * (hi[a] - lo[a]) : 0.0;
-            b.c[a] = c;
-            b.h[a] = __double2float_ru(hh) * (1.0f + 1e-6f);
-        }
-        b.first = B * kBlockTiles;
-        b.ntiles = min(kBlockTiles, nkids - B * kBlockTiles);
-        b.pad = 0.f;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// traversal
-// ---------------------------------------------------------------------------
-template <int D>
-struct Query {
-    double ow[D];   // wave origin (query tile centre, transformed), uniform
-    float ew[D];    // half-extents of the query tile around ow, uniform, conservative
-    float pw[D];    // lane point relative to ow, fp32
-    double p64[D];  // lane point, fp64 (transformed)
-    bool valid;
-};
-
-// squared gap between the wave box (ow +- ew) and a box (c +- h); conservative in fp32
-template <int D>
-__device__ __forceinline__ float gap2_box(const Query<D>& q, const double* c, const float* h) {
-    float g2 = 0.f;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const float dl = fabsf((float)(q.ow[a] - c[a]));
-        float g = dl - q.ew[a] - h[a];
-        g -= (dl + q.ew[a] + h[a]) * 9.5367431640625e-7f;  // 2^-20 slack
-        g = fmaxf(g, 0.f);
-        g2 = fmaf(g, g, g2);
-    }
-    return g2;
-}
-
-// The query box of the lanes where `on` holds (the wave's lanes still searching): their fp32 offsets
-// pw lie within ow' +- ew' (conservative: the centre is rounded, the half-extent padded).  A list
-// walk or fallback tests candidate tiles against it instead of the whole source tile's box, so a
-// wave with a few searching lanes visits only the tiles near them (the list, built for the whole
-// box, covers any subset of its lanes).  Values are shifted by 2 ew (>= |pw|) to use the
-// non-negative wave max; lanes with on = false pass the negative marker.
-template <int D>
-__device__ __forceinline__ Query<D> active_box(const Query<D>& q, bool on) {
-    Query<D> qa = q;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        const float B = 2.f * q.ew[a] + 1e-30f;
-        const float hi = wave_maxf(on ? q.pw[a] + B : -1.f) - B;
-        const float lo = B - wave_maxf(on ? B - q.pw[a] : -1.f);
-        const float mid = 0.5f * (lo + hi);
-        qa.ow[a] = q.ow[a] + (double)mid;
-        qa.ew[a] = 0.5f * (hi - lo) + 4.8e-7f * (fabsf(lo) + fabsf(hi) + B) + 1e-30f;
-    }
-    return qa;
-}
-
-// Two-level culled walk over the database tiles.  `visit(T)` returns true when it
-// processed the tile (the wave's bound then shrinks); `wave_bound()` is the max over
-// lanes of the squared search radius still needed.
-// With skin > 0 every tile whose box lies within sqrt(wb) + skin of the wave box is also passed
-// to collect(T) (wb as it stands when the tile is tested; wb only shrinks, so at the end the
-// collected set holds every tile within sqrt(wb_final) + skin).
-struct NoCount {
-    __device__ __forceinline__ void count(int, unsigned = 1) {}
-};
-template <int D, class Visit, class WB, class Collect, class Cnt = NoCount>
-__device__ __forceinline__ void traverse_c(const DevCloud& db, const Query<D>& q, int seed, Visit&& visit,
-                                           WB&& wave_bound, float skin, Collect&& collect, Cnt* cnt = nullptr) {
-    const int l = lane_id();
-    auto infl = [&](float w) -> float {
-        if (skin <= 0.f || w < 0.f) return w;
-        const float r = __builtin_amdgcn_sqrtf(w) * 1.0001f + skin;
-        return r * r;
-    };
-    float wb = wave_bound();
-    float wbi = infl(wb);
-    if (seed >= 0) {
-        collect(seed);
-        if (visit(seed)) {
-            wb = wave_bound();
-            wbi = infl(wb);
-        }
-    }
-    // super-blocks (64 blocks each, stored after the blocks): a round of 64 block tests is one
-    // super-block, skipped whole when its box (scalar loads, uniform test) is out of reach.  It contains
-    // its blocks' boxes, so the visited tiles and their order are unchanged.
-    typedef __attribute__((address_space(4))) const BlockInfo* ConstBlocks;
-    const ConstBlocks cb0 = (ConstBlocks)(uintptr_t)db.blocks + db.nblocks;
-    for (int b0 = 0; b0 < db.nblocks; b0 += kWave) {
-        {
-            const ConstBlocks sb = cb0 + (b0 / kWave);
-            const double c[3] = {sb->c[0], sb->c[1], sb->c[2]};
-            const float h[3] = {sb->h[0], sb->h[1], sb->h[2]};
-            if (!__builtin_amdgcn_readfirstlane((int)(gap2_box<D>(q, c, h) <= wbi))) continue;   // uniform
-        }
-        if (cnt) cnt->count(5);
-        const int b = b0 + l;
-        bool cb = false;
-        if (b < db.nblocks) cb = gap2_box<D>(q, db.blocks[b].c, db.blocks[b].h) <= wbi;
-        uint64_t bm = __ballot(cb);
-        while (bm) {
-            const int bb = b0 + __ffsll((unsigned long long)bm) - 1;
-            bm &= bm - 1;
-            const int first = db.blocks[bb].first, nt = db.blocks[bb].ntiles;
-            if (cnt) cnt->count(6);
-            const int t = first + l;
-            bool ct = false, cv = false;
-            if (l < nt && t != seed) {
-                const float g2 = gap2_box<D>(q, db.tiles[t].c, db.tiles[t].h);
-                ct = g2 <= wbi;
-                cv = g2 <= wb;
-            }
-            if (skin > 0.f) {
-                uint64_t cm = __ballot(ct);
-                while (cm) {
-                    collect(first + __ffsll((unsigned long long)cm) - 1);
-                    cm &= cm - 1;
-                }
-            }
-            uint64_t tm = __ballot(cv);
-            while (tm) {
-                const int T = first + __ffsll((unsigned long long)tm) - 1;
-                tm &= tm - 1;
-                if (visit(T)) {
-                    wb = wave_bound();
-                    wbi = infl(wb);
-                }
-            }
-        }
-    }
-}
-
-template <int D, class Visit, class WB>
-__device__ __forceinline__ void traverse(const DevCloud& db, const Query<D>& q, int seed, Visit&& visit,
-                                         WB&& wave_bound) {
-    traverse_c<D>(db, q, seed, visit, wave_bound, 0.f, [](int) {});
-}
-
-// per-wave LDS: tile staging during the walk, statistics transpose afterwards (same bytes)
-struct WaveStage {
-    float x[kTile], y[kTile], z[kTile];           // fp32 screen coordinates, SoA
-    double x64[kTile], y64[kTile], z64[kTile];    // fp64 coordinates (covariance sums, fallback)
-    int32_t perm[kTile];                          // original indices (fallback tie-break)
-};
-// statistics transpose image of 32 points (half a wave): u[term][point] and v[term][point], rows padded
-// to 33 doubles.  A term's 32 points are written by 32 lanes to consecutive words.  An MFMA operand read
-// takes row l & 15 at column c + (l >> 4); the compiler pairs the reads of two MFMAs into ds_read2_b64
-// (banks of 4 B modulo 32, conflicts within 16 consecutive lanes, which share l >> 4): rows r = 0..15 at
-// doubles 33 r + const fall on the bank pairs 2 r + const, all distinct.  An even stride collides: 34 put
-// rows r and r + 8 on one bank (SQ_LDS_BANK_CONFLICT 124 cycles per wave against 6 at 33 and at the former
-// 17, profiles/epilogue/README.md); lone ds_read_b64 (modulo 64, 32-lane halves) would want 34 instead.
-// Only the rows of terms in use are stored (12 u and 10 v terms in 3-D): the MFMA lanes of the unused
-// rows read a duplicate of the last row, whose products land in output rows / columns nobody reads.
-// 22 x 33 doubles (5808 B) per wave: two transposes per wave instead of four, at 22.7 KB of LDS per
-// workgroup -- the six workgroups that 80 VGPRs allow on a CU take 136 of its 160 KiB.
-constexpr int kStatRow = 33;
-constexpr int kStatU = 12, kStatV = 10;
-struct WaveStat {
-    double u[kStatU * kStatRow];
-    double v[kStatV * kStatRow];
-};
-union __attribute__((aligned(16))) WaveLds {
-    WaveStage t;
-    WaveStat st;
-};
-
-// Lane point relative to database tile T, and the per-lane squared gap to T's box.
-template <int D>
-__device__ __forceinline__ float lane_gap2(const Query<D>& q, const TileInfo& ti, float* pr) {
-    float g2 = 0.f;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        pr[a] = q.pw[a] + (float)(q.ow[a] - ti.c[a]);
-        const float ap = fabsf(pr[a]);
-        float g = ap - ti.h[a] - (ap + ti.h[a]) * 9.5367431640625e-7f;
-        g = fmaxf(g, 0.f);
-        g2 = fmaf(g, g, g2);
-    }
-    return g2;
-}
-
-// uniform copy of a tile's metadata through the constant address space: scalar s_load_dwordx*
-// into SGPRs (a generic pointer here compiles to ten vector loads + readfirstlane)
-typedef __attribute__((address_space(4))) const TileInfo* ConstTiles;
-__device__ __forceinline__ TileInfo tile_meta(const DevCloud& db, int T) {
-    const ConstTiles ct = (ConstTiles)(uintptr_t)db.tiles + __builtin_amdgcn_readfirstlane(T);
-    TileInfo t;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        t.c[a] = ct->c[a];
-        t.h[a] = ct->h[a];
-    }
-    t.start = ct->start;
-    t.count = ct->count;
-    t.radius = ct->radius;
-#pragma unroll
-    for (int g = 0; g < kSub; ++g)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            t.sc[a][g] = ct->sc[a][g];
-            t.sh[a][g] = ct->sh[a][g];
-        }
-    return t;
-}
-
-// stage a tile's fp32 coordinates (padding rows at 1e30: their distance is +inf)
-__device__ __forceinline__ void stage_f32(const DevCloud& db, const TileInfo& ti, WaveLds& L) {
-    const int l = lane_id();
-    float4 v = make_float4(1e30f, 1e30f, 1e30f, 0.f);
-    if (l < ti.count) v = db.rel32[ti.start + l];
-    L.t.x[l] = v.x;
-    L.t.y[l] = v.y;
-    L.t.z[l] = v.z;
-    wave_sync();
-}
-__device__ __forceinline__ float4 load_rel(const DevCloud& db, int start, int count) {
-    const int l = lane_id();
-    float4 v = make_float4(1e30f, 1e30f, 1e30f, 0.f);
-    if (l < count) v = db.rel32[start + l];
-    return v;
-}
-__device__ __forceinline__ void stage_f32_from(const float4& v, WaveLds& L) {
-    const int l = lane_id();
-    L.t.x[l] = v.x;
-    L.t.y[l] = v.y;
-    L.t.z[l] = v.z;
-    wave_sync();
-}
-// k_corr's full walk: traverse_c's order and culling, but each lane of a candidate block holds its
-// tile's box gap and (start, count), so a candidate's coordinates are requested together with its
-// metadata (visit_pre(T, &coords): one memory round trip per visited tile instead of two), and
-// candidates the shrinking bound has put out of reach are dropped before they are visited (the test the
-// block entry applied, repeated with the current bound; a tile it drops could not have been within
-// any lane's bound).
-template <int D, class VisitPre, class WB, class Collect, class Cnt = NoCount>
-__device__ __forceinline__ void walk_c(const DevCloud& db, const Query<D>& q, int seed, VisitPre&& visit_pre,
-                                       WB&& wave_bound, float skin, Collect&& collect, Cnt* cnt = nullptr) {
-    const int l = lane_id();
-    auto infl = [&](float w) -> float {
-        if (skin <= 0.f || w < 0.f) return w;
-        const float r = __builtin_amdgcn_sqrtf(w) * 1.0001f + skin;
-        return r * r;
-    };
-    float wb = wave_bound();
-    float wbi = infl(wb);
-    if (seed >= 0) {
-        collect(seed);
-        if (visit_pre(seed, nullptr)) {
-            wb = wave_bound();
-            wbi = infl(wb);
-        }
-    }
-    // super-blocks (64 blocks each, stored after the blocks): lane s tests super-block s0 + s, all of a
-    // round of 64 requested at once (one memory round trip instead of one per super-block); a candidate
-    // super-block's 64 blocks are tested by the lanes, a candidate block's 64 tiles likewise from the
-    // compact TileBox records (block b's tiles are 64 b .. 64 b + 63).  Same tiles, same order as the
-    // one-super-block-at-a-time walk.
-    const int nsuper = (db.nblocks + kWave - 1) / kWave;
-    for (int s0 = 0; s0 < nsuper; s0 += kWave) {
-        float sg = 3e38f;
-        if (s0 + l < nsuper) sg = gap2_box<D>(q, db.blocks[db.nblocks + s0 + l].c, db.blocks[db.nblocks + s0 + l].h);
-        uint64_t sm = __ballot(sg <= wbi);
-        while (sm) {
-            const int sl = __ffsll((unsigned long long)sm) - 1;
-            sm &= sm - 1;
-            const int b0 = (s0 + sl) * kWave;
-            if (cnt) cnt->count(5);
-            const int b = b0 + l;
-            bool cb = false;
-            if (b < db.nblocks) cb = gap2_box<D>(q, db.blocks[b].c, db.blocks[b].h) <= wbi;
-            uint64_t bm = __ballot(cb);
-            while (bm) {
-                const int bb = b0 + __ffsll((unsigned long long)bm) - 1;
-                bm &= bm - 1;
-                const int first = bb * kBlockTiles, nt = min(kBlockTiles, db.ntiles - first);
-                if (cnt) cnt->count(6);
-                const int t = first + l;
-                bool ct = false;
-                float g2 = 3e38f;
-                int tst = 0, tcnt = 0;   // the tile's start, count
-                if (l < nt && t != seed) {
-                    const TileBox tb = db.boxes[t];
-                    g2 = gap2_box<D>(q, tb.c, tb.h);
-                    ct = g2 <= wbi;
-                    tst = tb.start;
-                    tcnt = tb.count;
-                }
-                if (skin > 0.f) {
-                    uint64_t cm = __ballot(ct);
-                    while (cm) {
-                        collect(first + __ffsll((unsigned long long)cm) - 1);
-                        cm &= cm - 1;
-                    }
-                }
-                uint64_t tm = __ballot(g2 <= wb);
-                auto pick = [&]() -> int { return tm ? __ffsll((unsigned long long)tm) - 1 : -1; };
-                auto coords = [&](int kk) {
-                    return load_rel(db, __builtin_amdgcn_readlane(tst, kk), __builtin_amdgcn_readlane(tcnt, kk));
-                };
-                for (int k = pick(); k >= 0; k = pick()) {
-                    tm &= ~(1ull << k);
-                    const float4 pv = coords(k);   // in flight with the tile's metadata load in visit_pre
-                    if (visit_pre(first + k, &pv)) {
-                        wb = wave_bound();
-                        wbi = infl(wb);
-                        tm &= __ballot(g2 <= wb);
-                    }
-                }
-            }
-        }
-    }
-}
-
-__device__ __forceinline__ void stage_f64(const DevCloud& db, const TileInfo& ti, WaveLds& L) {
-    const int l = lane_id();
-    double4 v;
-    v.x = v.y = v.z = 1e150;
-    v.w = 0.0;
-    if (l < ti.count) v = reinterpret_cast<const double4*>(db.xyz64)[ti.start + l];
-    L.t.x64[l] = v.x;
-    L.t.y64[l] = v.y;
-    L.t.z64[l] = v.z;
-    wave_sync();
-}
-
-typedef float f2v __attribute__((ext_vector_type(2)));
-
-// squared screen distance of the lane point to two database rows at once (v_pk_* fp32);
-// bit-identical to fmaf(dz, dz, fmaf(dy, dy, dx * dx)) per row
-template <int D>
-__device__ __forceinline__ f2v pair_d2(const float* pr, f2v qx, f2v qy, f2v qz) {
-    const f2v dx = f2v{pr[0], pr[0]} - qx;
-    const f2v dy = f2v{pr[1], pr[1]} - qy;
-    f2v d2 = __builtin_elementwise_fma(dy, dy, dx * dx);
-    if (D == 3) {
-        const f2v dz = f2v{pr[2], pr[2]} - qz;
-        d2 = __builtin_elementwise_fma(dz, dz, d2);
-    }
-    return d2;
-}
-
-// 0xFFFFFFC0 held in a VGPR so (d2 & mask) | row is one v_and_or_b32 (row stays an SGPR)
-__device__ __forceinline__ unsigned key_mask() {
-    unsigned m;
-    asm volatile("v_mov_b32 %0, 0xffffffc0" : "=v"(m));
-    return m;
-}
-
-// One group of 4 rows at compile-time offset J: 3 ds_read_b128 (SoA x/y/z), 2 packed pairs.
-template <int J, int D, class Row>
-__device__ __forceinline__ void scan_group(const WaveLds& L, const float* pr, unsigned M, Row& row) {
-    const float4 X = *reinterpret_cast<const float4*>(L.t.x + J);
-    const float4 Y = *reinterpret_cast<const float4*>(L.t.y + J);
-    float4 Z = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (D == 3) Z = *reinterpret_cast<const float4*>(L.t.z + J);
-    const f2v a = pair_d2<D>(pr, f2v{X.x, X.y}, f2v{Y.x, Y.y}, f2v{Z.x, Z.y});
-    const f2v b = pair_d2<D>(pr, f2v{X.z, X.w}, f2v{Y.z, Y.w}, f2v{Z.z, Z.w});
-    row((__float_as_uint(a.x) & M) | (unsigned)J, J);
-    row((__float_as_uint(a.y) & M) | (unsigned)(J + 1), J + 1);
-    row((__float_as_uint(b.x) & M) | (unsigned)(J + 2), J + 2);
-    row((__float_as_uint(b.y) & M) | (unsigned)(J + 3), J + 3);
-}
-
-template <int D, class Row, int... G>
-__device__ __forceinline__ void scan_groups(const WaveLds& L, int n4, unsigned sub, const float* pr, unsigned M,
-                                            Row& row, std::integer_sequence<int, G...>) {
-    // short-circuit fold: group G runs only while 4G < n4; skipped when its sub-tile is not needed
-    (void)((4 * G < n4 ? (((sub >> (4 * G / kSubRows)) & 1u) ? scan_group<4 * G, D>(L, pr, M, row) : void(), true) : false) &&
-           ...);
-}
-
-// Per-lane squared gap to each sub-box of the staged tile; bit g of the result is set when
-// some lane within its bound needs sub-tile g.  Same conservative slack as lane_gap2.
-template <int D>
-__device__ __forceinline__ unsigned sub_mask(const TileInfo& ti, const float* pr, bool valid, float bound) {
-    unsigned m = 0;
-#pragma unroll
-    for (int g = 0; g < kSub; ++g) {
-        if (kSubRows * g >= ti.count) break;
-        float g2 = 0.f;
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            const float dl = fabsf(pr[a] - ti.sc[a][g]);
-            float gg = dl - ti.sh[a][g] - (dl + ti.sh[a][g] + fabsf(pr[a])) * 9.5367431640625e-7f;
-            gg = fmaxf(gg, 0.f);
-            g2 = fmaf(gg, gg, g2);
-        }
-        if (__any(valid && g2 <= bound)) m |= 1u << g;
-    }
-    return m;
-}
-
-// k_corr's forms of lane_gap2 / sub_mask: no per-axis rounding slack; the caller compares against a
-// bound inflated once by the launch-uniform slack S (CorrArgs::gap_slack: rounding of coordinates
-// of magnitude <= sqrt(search2) + 2 rho_t, the only ones whose test can matter)
-template <int D>
-__device__ __forceinline__ float lane_gap2_ns(const Query<D>& q, const TileInfo& ti, float* pr) {
-    float g2 = 0.f;
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        pr[a] = q.pw[a] + (float)(q.ow[a] - ti.c[a]);
-        const float g = fmaxf(fabsf(pr[a]) - ti.h[a], 0.f);
-        g2 = fmaf(g, g, g2);
-    }
-    return g2;
-}
-template <int D>
-__device__ __forceinline__ unsigned sub_mask_ns(const TileInfo& ti, const float* pr, float bound /* < 0: lane off */) {
-    // two sub-boxes per packed op (sc/sh are axis-major, so boxes g and g+1 of an axis are adjacent):
-    // g = max(max(d, -d) - sh, 0), g2 += g * g
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    unsigned m = 0;
-#pragma unroll
-    for (int g = 0; g < kSub; g += 2) {
-        if (kSubRows * g >= ti.count) break;
-        f2v g2 = {0.f, 0.f};
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            const f2v d = f2v{pr[a], pr[a]} - f2v{ti.sc[a][g], ti.sc[a][g + 1]};
-            const f2v ad = __builtin_elementwise_max(d, -d);
-            const f2v gg = __builtin_elementwise_max(ad - f2v{ti.sh[a][g], ti.sh[a][g + 1]}, f2v{0.f, 0.f});
-            g2 = __builtin_elementwise_fma(gg, gg, g2);
-        }
-        if (wave_any(g2.x <= bound)) m |= 1u << g;
-        if (kSubRows * (g + 1) < ti.count && wave_any(g2.y <= bound)) m |= 2u << g;
-    }
-    return m;
-}
-
-__device__ __forceinline__ int rows_scanned(unsigned sub, int count) {
-    int r = 0;
-#pragma unroll
-    for (int g = 0; g < kSub; ++g)
-        if ((sub >> g) & 1u) r += min(kSubRows, max(0, ((count + 3) & ~3) - kSubRows * g));
-    return r;
-}
-
-// Scan one staged tile: row(key, j) for every row of the sub-tiles in `sub`; key = (d2 bits & ~63) | row.
-template <int D, class Row>
-__device__ __forceinline__ void scan_tile(const WaveLds& L, int count, const float* pr, Row&& row,
-                                          unsigned sub = 0xFFFFFFFFu) {
-    const unsigned M = key_mask();
-    scan_groups<D>(L, (count + 3) & ~3, sub, pr, M, row, std::make_integer_sequence<int, kTile / 4>{});
-}
-
-// (the covariance helpers CovSums, cov_add, smallest_eigvec3 and cov_descriptor: gicp_cov_dev.h)
-
-// The wave's query for split build kernels: wave `wid` takes part g = wid % split of query tile
-// T = first + wid / split.  Lanes keep their points relative to the tile centre (the screen's error model
-// is unchanged); the culling box `qb` is the part's sub-box (centre c + sc, half-extents sh) when split.
-// Returns the tile index, -1 if the wave has no rows.
-template <int D>
-__device__ __forceinline__ int split_query(const DevCloud& cl, int first, int last, int split, int sh_n, int sh_r,
-                                          TileInfo& qt, Query<D>& q, Query<D>& qb, int& i) {
-    const int wid = (int)blockIdx.x * kWavesPerWG + ((int)threadIdx.x >> 6), l = (int)threadIdx.x & 63;
-    const int Tl = first + wid / split, g = wid % split;
-    if (Tl >= last) return -1;
-    constexpr int kChunkTiles = kShardChunk * kCorrWaves;   // tiles per shard chunk (k_corr's split)
-    const int T = sh_n > 1 ? ((Tl / kChunkTiles) * sh_n + sh_r) * kChunkTiles + Tl % kChunkTiles : Tl;
-    if (T >= cl.ntiles) return -1;
-    qt = tile_meta(cl, T);
-    const int rows = kTile / split, r0 = g * rows, r1 = min(qt.count, r0 + rows);
-    if (r0 >= r1) return -1;
-    q.valid = l < r1 - r0;
-    i = qt.start + r0 + min(l, r1 - r0 - 1);
-    const float4 rel = cl.rel32[i];
-    const double4 p4 = reinterpret_cast<const double4*>(cl.xyz64)[i];
-    const float relv[3] = {rel.x, rel.y, rel.z};
-    const double p4v[3] = {p4.x, p4.y, p4.z};
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        q.ow[a] = qt.c[a];
-        q.ew[a] = qt.h[a];
-        q.pw[a] = relv[a];
-        q.p64[a] = p4v[a];
-    }
-    qb = q;
-    if (split > 1) {
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            qb.ow[a] = qt.c[a] + (double)qt.sc[a][g];
-            qb.ew[a] = qt.sh[a][g] * (1.0f + 4.8e-7f) + 1e-30f;
-        }
-    }
-    return T;
-}
-
-// G: the target's neighbour graph rows come out of the same two walks: phase 1 keeps the
-// KL = max(K + 1, kGraphK + 2) smallest keys (the covariance uses the first K + 1, the graph all), phase 2
-// visits every tile either needs and takes each row for the covariance sums (key <= tau) and / or the
-// graph row (key <= tau_g).  Tiles are visited in the same order whatever the bound, so the sums and rows
-// are those of separate walks, bit for bit.
-template <int D, int K, bool G>
-__global__ void __launch_bounds__(256) k_knn_cov(CovArgs A) {
-    __shared__ WaveLds s_lds[kWavesPerWG];
-    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    WaveLds& L = s_lds[w];
-    const DevCloud& cl = A.cl;
-    TileInfo qt;
-    Query<D> q, qb;
-    int i = 0;
-    const int T = split_query<D>(cl, A.q_begin, A.q_end, A.split, A.sh_n, A.sh_r, qt, q, qb, i);
-    if (T < 0) return;  // waves are independent (no workgroup barrier here)
-
-    // ---- phase 1: fp32 screen for the K+1 smallest keys ------------------
-    constexpr int K1 = K + 1, KG = kGraphK, KL = G ? (K1 > KG + 2 ? K1 : KG + 2) : K1;
-    const unsigned init = __float_as_uint(A.search2) | 63u;
-    unsigned lk[KL];
-#pragma unroll
-    for (int m = 0; m < KL; ++m) lk[m] = init;
-    auto lane_bound = [&]() -> float {
-        if (!q.valid) return -1.f;
-        if (G) return key_d2(lk[KL - 1]);   // >= the covariance's own bound below
-        const float kk = key_d2(lk[K1 - 1]), km = key_d2(lk[K1 - 2]);
-        return fminf(kk, km + 2.f * marg(A.mg, km));
-    };
-    auto visit1 = [&](int Tt) -> bool {
-        const TileInfo ti = tile_meta(cl, Tt);
-        float pr[D];
-        const bool need = lane_gap2<D>(q, ti, pr) <= lane_bound();
-        if (!__any(need)) return false;
-        // sub-tiles beyond the top of the truncation bucket of each lane's last list key hold no row the
-        // list would take (a key below it screens at most at that bucket's top)
-        const unsigned sub = sub_mask<D>(ti, pr, q.valid, __uint_as_float((lk[KL - 1] | 63u) + 1u));
-        stage_f32(cl, ti, L);
-        scan_tile<D>(L, ti.count, pr, [&](unsigned key, int) {
-            if (__any(key < lk[KL - 1])) {
-#pragma unroll
-                for (int m = KL - 1; m > 0; --m) lk[m] = umed3(lk[m - 1], lk[m], key);
-                lk[0] = min(lk[0], key);
-            }
-        }, sub);
-        wave_sync();
-        return true;
-    };
-    traverse<D>(cl, qb, T, visit1, [&]() { return wave_maxf(lane_bound()); });
-
-    // graph: rows keyed <= tau_g (the (kGraphK + 1)-th key, self excluded from the row) and the radius the
-    // row certifies (k_graph's rules: from the (kGraphK + 2)-th key, or the screen radius)
-    unsigned tau_g = 0;
-    float r2g = 0.f, tau_g_hi = -1.f;
-    if constexpr (G) {
-        tau_g = lk[KG];
-        if (lk[KG + 1] >= init) {
-            r2g = A.search2 - marg(A.mg, A.search2);
-        } else {
-            const float kd = key_d2(lk[KG + 1] > tau_g ? lk[KG + 1] : tau_g);
-            r2g = kd - marg(A.mg, kd);
-        }
-        tau_g_hi = tau_g >= init ? A.search2 : __uint_as_float((tau_g | 63u) + 1u);
-    }
-
-    int c = 0;
-#pragma unroll
-    for (int m = 0; m < K1; ++m) c += lk[m] < init ? 1 : 0;
-    const int nacc = min(c, K);
-    unsigned tau = init;
-#pragma unroll
-    for (int m = 0; m < K; ++m)
-        if (m == nacc - 1) tau = lk[m];
-    const float tau_d2 = key_d2(tau);
-    bool amb = false;
-    if (c > K) {
-        const float a1 = key_d2(lk[K - 1]), a2 = key_d2(lk[K]);
-        amb = (a2 - a1) <= marg(A.mg, a1) + marg(A.mg, a2);
-    }
-    const float dn2_lo = (float)A.dn2 * (1.0f - 2.4e-7f);
-    if (tau_d2 + marg(A.mg, tau_d2) >= dn2_lo) amb = true;
-    amb = amb && q.valid;
-
-    // ---- phase 2: fp64 shifted sums over the accepted keys ------------------
-    CovSums<D> S;
-    S.n = 0.0;
-#pragma unroll
-    for (int a = 0; a < D; ++a) S.s[a] = 0.0;
-#pragma unroll
-    for (int k = 0; k < D * (D + 1) / 2; ++k) S.ss[k] = 0.0;
-    const bool take_lane = q.valid && !amb;
-    // cull by the top of tau's truncation bucket: a point keyed <= tau may screen above key_d2(tau)
-    const float tau_hi = __uint_as_float((tau | 63u) + 1u);
-    // the lane's phase-2 bound: the covariance's, and the graph row's
-    const float b2 = fmaxf(take_lane ? tau_hi : -1.f, (G && q.valid) ? tau_g_hi : -1.f);
-    int gcnt = 0;
-    bool gover = false;
-    float4* row_out = G ? A.g_nb + (int64_t)i * KG : nullptr;
-    auto visit2 = [&](int Tt) -> bool {
-        const TileInfo ti = tile_meta(cl, Tt);
-        float pr[D];
-        const bool need = lane_gap2<D>(q, ti, pr) <= b2;
-        if (!__any(need)) return false;
-        const unsigned sub = sub_mask<D>(ti, pr, b2 >= 0.f, b2);
-        stage_f32(cl, ti, L);
-        stage_f64(cl, ti, L);
-        scan_tile<D>(L, ti.count, pr, [&](unsigned key, int j) {
-            const bool take = take_lane && key <= tau;
-            if (__any(take)) {
-                const double qq[3] = {L.t.x64[j], L.t.y64[j], L.t.z64[j]};
-                double d[D];
-#pragma unroll
-                for (int a = 0; a < D; ++a) d[a] = qq[a] - q.p64[a];
-                if (take) cov_add<D>(S, d);
-            }
-            if constexpr (G) {
-                const int t = ti.start + j;
-                if (q.valid && key <= tau_g && t != i) {
-                    if (gcnt < KG) {
-                        const double qq[3] = {L.t.x64[j], L.t.y64[j], L.t.z64[j]};
-                        float v[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int a = 0; a < D; ++a) v[a] = (float)(qq[a] - q.p64[a]);
-                        row_out[gcnt] = make_float4(v[0], v[1], v[2], __int_as_float(t));
-                        ++gcnt;
-                    } else {
-                        gover = true;
-                    }
-                }
-            }
-        }, sub);
-        wave_sync();
-        return true;
-    };
-    traverse<D>(cl, qb, T, visit2, [&]() { return wave_maxf(b2); });
-    if (G && q.valid) {
-        // r rounded down; an overflowing row (ties at tau beyond kGraphK) certifies nothing
-        const float r = gover ? 0.f : __builtin_amdgcn_sqrtf(fmaxf(r2g, 0.f)) * 0.99999f;
-        A.g_nbh[i] = make_float2(r, __int_as_float(gcnt));
-    }
-
-    // ---- fp64 fallback for lanes the screen could not decide ----------------
-    if (__any(amb)) {
-        if (A.amb_counter && l == 0) atomicAdd(A.amb_counter, __popcll(__ballot(amb)));
-        double lk64[K];
-#pragma unroll
-        for (int m = 0; m < K; ++m) lk64[m] = A.dn2;
-        const float bound_f = A.search2;
-        auto visit3 = [&](int Tt) -> bool {
-            const TileInfo ti = tile_meta(cl, Tt);
-            float pr[D];
-            const float b64 = (float)lk64[K - 1];
-            const bool need = amb && lane_gap2<D>(q, ti, pr) <= b64 + 2.f * marg(A.mg, b64);
-            if (!__any(need)) return false;
-            stage_f64(cl, ti, L);
-            for (int j = 0; j < ti.count; ++j) {
-                const double qq[3] = {L.t.x64[j], L.t.y64[j], L.t.z64[j]};
-                const double d2 = dist2_exact<D>(qq, q.p64);
-                if (__any(amb && d2 < lk64[K - 1])) {
-                    if (amb) {
-#pragma unroll
-                        for (int m = K - 1; m > 0; --m) lk64[m] = fmin(lk64[m], fmax(lk64[m - 1], d2));
-                        lk64[0] = fmin(lk64[0], d2);
-                    }
-                }
-            }
-            wave_sync();
-            return true;
-        };
-        traverse<D>(cl, qb, T, visit3, [&]() { return wave_maxf(amb ? bound_f : -1.f); });
-        int c64 = 0;
-#pragma unroll
-        for (int m = 0; m < K; ++m) c64 += lk64[m] < A.dn2 ? 1 : 0;
-        double tau64 = A.dn2;
-#pragma unroll
-        for (int m = 0; m < K; ++m)
-            if (m == c64 - 1) tau64 = lk64[m];
-        int nless = 0;
-#pragma unroll
-        for (int m = 0; m < K; ++m) nless += lk64[m] < tau64 ? 1 : 0;
-        int eq_left = c64 - nless;
-        auto visit4 = [&](int Tt) -> bool {
-            const TileInfo ti = tile_meta(cl, Tt);
-            float pr[D];
-            const float b64 = (float)tau64;
-            const bool need = amb && lane_gap2<D>(q, ti, pr) <= b64 + 2.f * marg(A.mg, b64);
-            if (!__any(need)) return false;
-            stage_f64(cl, ti, L);
-            for (int j = 0; j < ti.count; ++j) {
-                const double qq[3] = {L.t.x64[j], L.t.y64[j], L.t.z64[j]};
-                const double d2 = dist2_exact<D>(qq, q.p64);
-                bool take = amb && c64 > 0 && (d2 < tau64 || (d2 == tau64 && eq_left > 0));
-                if (take && d2 == tau64) --eq_left;
-                if (__any(take)) {
-                    double d[D];
-#pragma unroll
-                    for (int a = 0; a < D; ++a) d[a] = qq[a] - q.p64[a];
-                    if (take) cov_add<D>(S, d);
-                }
-            }
-            wave_sync();
-            return true;
-        };
-        traverse<D>(cl, qb, T, visit4, [&]() {
-            const float b64 = (float)tau64;
-            return wave_maxf(amb ? b64 + 2.f * marg(A.mg, b64) : -1.f);
-        });
-    }
-
-    if (q.valid) {
-        A.cov_out[i] = cov_descriptor<D>(S, A.min_nb, A.eps_a, A.m_scale);
-        A.count_out[i] = (int)S.n;
-    }
-}
-
-// ---------------------------------------------------------------------------
-// target neighbour graph: for every target point i its kGraphK nearest other target
-// points (relative positions + sorted indices) and a radius r(i) such that EVERY target t != i with true
-// |x_t - x_i| < r(i) is in the row.  Built once per target cloud by k_knn_cov<D, K, true> (the same walks
-// as the covariances); k_corr's graph descent proves nearest neighbours with it.  Only conservativeness of
-// r matters (no tie rules): phase 1 keeps the kGraphK + 2 smallest screened keys (self included); phase 2
-// emits the rows keyed <= tau = the (kGraphK + 1)-th key, self excluded; a row not emitted has a screened
-// key > tau, so its true d2 >= key_d2(lk[kGraphK + 1]) - margin when that key is above tau (else
-// key_d2(tau) - margin); a lane that found fewer keys within the screen radius has every target within it:
-// r2 = search2 - margin.
-// Pack the graph rows (DevCloud::nbq / nbx): offsets quantised to int16 in units of s = max |offset| / 32767
-// (error <= s / 2 per axis, which k_corr's bound adds), entries ordered nearest-first, each with its
-// sorted-index delta (kGraphFar when it does not fit 16 bits), so a descent step finds the next node without
-// reading nbi.
-__global__ void __launch_bounds__(256) k_graph_pack(const float4* __restrict__ nb, const float2* __restrict__ nbh,
-                                                    int64_t n, uint4* __restrict__ nbq, uint4* __restrict__ nbx,
-                                                    int32_t* __restrict__ nbi) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float2 h = nbh[i];
-    const int cnt = __float_as_int(h.y);
-    float m = 0.f;
-    for (int k = 0; k < cnt; ++k) {
-        const float4 v = nb[i * kGraphK + k];
-        m = fmaxf(m, fmaxf(fabsf(v.x), fmaxf(fabsf(v.y), fabsf(v.z))));
-    }
-    const float s = m > 0.f ? m / 32767.f : 1e-30f;
-    const float inv = 1.f / s;
-    // entries nearest-first (squared offset length, ties by sorted index): k_corr's descent reads the first
-    // half-line and needs the rest only when an entry there could still be the nearest
-    float key[kGraphK];
-    int ord[kGraphK];
-    for (int k = 0; k < cnt; ++k) {
-        const float4 v = nb[i * kGraphK + k];
-        const float kk = fmaf(v.z, v.z, fmaf(v.y, v.y, v.x * v.x));
-        const int t = __float_as_int(v.w);
-        int pos = k;
-        while (pos > 0 && (key[pos - 1] > kk || (key[pos - 1] == kk && __float_as_int(nb[i * kGraphK + ord[pos - 1]].w) > t))) {
-            key[pos] = key[pos - 1];
-            ord[pos] = ord[pos - 1];
-            --pos;
-        }
-        key[pos] = kk;
-        ord[pos] = k;
-    }
-    uint32_t w[2 + 2 * kGraphK];
-    w[0] = __float_as_uint(h.x);
-    w[1] = __float_as_uint(s);
-    // unused entries (k >= cnt) repeat the last real entry (or the node itself, offset and delta 0, in an
-    // empty row), so the descent needs no per-entry validity test: a repeated entry never becomes the
-    // strictly nearer candidate and at most makes the runner-up equal the winner, which the descent
-    // treats as a near tie resolved exactly over the real entries (nbi = -1 marks the repeats)
-    int q[4] = {0, 0, 0, 0};
-    for (int k = 0; k < kGraphK; ++k) {
-        int idx = -1;
-        if (k < cnt) {
-            const float4 v = nb[i * kGraphK + ord[k]];
-            const float c[3] = {v.x, v.y, v.z};
-            for (int a = 0; a < 3; ++a) q[a] = max(-32767, min(32767, __float2int_rn(c[a] * inv)));
-            idx = __float_as_int(v.w);
-            const int64_t d = (int64_t)idx - i;
-            q[3] = d >= -32767 && d <= 32767 ? (int)d : kGraphFar;
-        }
-        w[2 + 2 * k] = ((uint32_t)q[0] & 0xFFFFu) | ((uint32_t)q[1] << 16);
-        w[3 + 2 * k] = ((uint32_t)q[2] & 0xFFFFu) | ((uint32_t)q[3] << 16);
-        nbi[i * kGraphK + k] = idx;
-    }
-    for (int c = 0; c < 8; ++c) nbq[i * 8 + c] = make_uint4(w[4 * c], w[4 * c + 1], w[4 * c + 2], w[4 * c + 3]);
-    uint32_t x[12] = {};
-    for (int k = 0; k < 2 * (kGraphK - kGraphLineA); ++k) x[k] = w[2 + 2 * kGraphLineA + k];
-    for (int c = 0; c < 3; ++c) nbx[i * 3 + c] = make_uint4(x[4 * c], x[4 * c + 1], x[4 * c + 2], x[4 * c + 3]);
-}
 
 // ---------------------------------------------------------------------------
 // per-iteration correspondences + weights + statistics
@@ -1147,90 +43,13 @@ __global__ void __launch_bounds__(256) k_graph_pack(const float4* __restrict__ n
 #define GICP_CORR_SGPR 100
 #endif
 
-template <int D>
-struct StatIdx {
-    static constexpr int NS = D * (D + 1) / 2;
-    static constexpr int pa(int p) { return D == 3 ? (p < 3 ? 0 : (p < 5 ? 1 : 2)) : (p < 2 ? 0 : 1); }
-    static constexpr int pb(int p) {
-        return D == 3 ? (p == 0 ? 0 : p == 1 ? 1 : p == 2 ? 2 : p == 3 ? 1 : 2) : (p == 0 ? 0 : 1);
-    }
-};
-
-// Where entry (p, q) of the statistics GEMM's 16x16 product u v^T goes in the statistics vector (DESIGN.md
-// §4), or kNoSlot: most of the product is not a statistic.  Each statistic has exactly one (p, q).
-constexpr int kNoSlot = 0xFF;
-template <int D>
-constexpr int stat_slot(int p, int q) {
-    constexpr int NS = D * (D + 1) / 2;
-    constexpr int oB = NS * NS, oC = oB + NS * D, oR = oC + NS, oT = oR + D * D, o0 = oT + D;
-    if (p < NS) {
-        if (q < NS) return p * NS + q;                       // A[ab][ij]
-        if (q < NS + D) return oB + p * D + (q - NS);        // B[ab][i]
-        if (q == NS + D) return oC + p;                      // C[ab]
-    } else if (p < NS + D) {
-        if (q >= NS && q < NS + D) return oR + (p - NS) * D + (q - NS);   // gR[a][i]
-        if (q == NS + D) return oT + (p - NS);                            // gt[a]
-    } else if (q == NS + D) {
-        if (p <= NS + D + 1) return o0 + (p - NS - D);       // c0, count
-        if (p == NS + D + 2) return nstat(D) + 3;            // sum |r|^2 (extended slot)
-    }
-    return kNoSlot;
-}
-// Lane l of v_mfma_f64_16x16x4_f64 holds product entries (p = (l >> 4) + 4 j, q = l & 15), j = 0..3: their
-// slots, one byte each (byte j), as one dword per lane
-template <int D>
-struct StatSlots {
-    uint32_t lane[64];
-    constexpr StatSlots() : lane{} {
-        for (int l = 0; l < 64; ++l) {
-            uint32_t w = 0;
-            for (int j = 0; j < 4; ++j) w |= (uint32_t)stat_slot<D>((l >> 4) + 4 * j, l & 15) << (8 * j);
-            lane[l] = w;
-        }
-    }
-};
-static_assert(nstat_ext(3) <= kNoSlot && nstat_ext(2) <= kNoSlot, "a statistic's slot fits a byte");
-// every statistic, and the extended sum |r|^2, has one owner among the 256 entries; no other slot is written
-template <int D>
-constexpr bool stat_slots_one_owner() {
-    int owners[kNoSlot] = {};
-    for (int p = 0; p < 16; ++p)
-        for (int q = 0; q < 16; ++q)
-            if (stat_slot<D>(p, q) != kNoSlot) ++owners[stat_slot<D>(p, q)];
-    for (int k = 0; k < kNoSlot; ++k)
-        if (owners[k] != ((k < nstat(D) || k == nstat(D) + 3) ? 1 : 0)) return false;
-    return true;
-}
-static_assert(stat_slots_one_owner<2>() && stat_slots_one_owner<3>(), "one owner lane per statistic");
+// the slot tables of the statistics GEMM (gicp_stats_dev.h StatSlots): device variables, so defined here alone
 __device__ const StatSlots<2> kStatSlots2{};
 __device__ const StatSlots<3> kStatSlots3{};
 template <int D>
 __device__ __forceinline__ uint32_t stat_slots(int l) {
     if constexpr (D == 2) return kStatSlots2.lane[l];
     else return kStatSlots3.lane[l];
-}
-
-// statistic k of one point: A[ab][ij], B[ab][i], C[ab], gR[a][i], gt[a], c0, count
-template <int D>
-__device__ __forceinline__ double stat_value(int k, const double (&W)[D][D], const double (&s)[D],
-                                             const double (&wr)[D], double rwr) {
-    using SI = StatIdx<D>;
-    constexpr int NS = SI::NS;
-    if (k < NS * NS) {
-        const int p = k / NS, qd = k % NS;
-        return W[SI::pa(p)][SI::pb(p)] * (s[SI::pa(qd)] * s[SI::pb(qd)]);
-    }
-    k -= NS * NS;
-    if (k < NS * D) return W[SI::pa(k / D)][SI::pb(k / D)] * s[k % D];
-    k -= NS * D;
-    if (k < NS) return W[SI::pa(k)][SI::pb(k)];
-    k -= NS;
-    if (k < D * D) return wr[k / D] * s[k % D];
-    k -= D * D;
-    if (k < D) return wr[k];
-    k -= D;
-    if (k == 0) return rwr;
-    return 1.0;
 }
 
 #ifndef GICP_SPARSE_GROUP
@@ -2845,244 +1664,8 @@ __global__ void __launch_bounds__(64) k_solve(IterState* S, double* hist) {
 }
 
 // ---------------------------------------------------------------------------
-// top-k of det(W) for the drop-in's visualisation extras (gicp.py:169-172)
-// ---------------------------------------------------------------------------
-// Order: larger det first, equal dets -> larger original index first, i.e. the last k positions of a
-// stable ascending argsort.  NaN (rows of other ranks' shards, memset 0xFF) never enters a list.
-constexpr int kTopMax = 16;
-
-__device__ __forceinline__ bool top_gt(double va, int64_t ia, double vb, int64_t ib) {
-    return va > vb || (va == vb && ia > ib);
-}
-
-// Each thread keeps its k best in registers (descending, unrolled so nothing spills), then the block
-// pops its k best with k rounds of a block-wide argmax over the threads' heads.
-struct TopList {
-    double v[kTopMax];
-    int64_t i[kTopMax];   // (original index << 32) | sorted position: ties order by the original index
-    __device__ void init() {
-#pragma unroll
-        for (int p = 0; p < kTopMax; ++p) {
-            v[p] = -INFINITY;
-            i[p] = -1;
-        }
-    }
-    __device__ void insert(double cv, int64_t ci, int k) {
-        if (!top_gt(cv, ci, -INFINITY, -1)) return;   // NaN / sentinel
-#pragma unroll
-        for (int p = 0; p < kTopMax; ++p) {
-            if (p < k && top_gt(cv, ci, v[p], i[p])) {
-                const double tv = v[p];
-                const int64_t ti = i[p];
-                v[p] = cv;
-                i[p] = ci;
-                cv = tv;
-                ci = ti;
-            }
-        }
-    }
-};
-
-__device__ void top_block_emit(TopList& L, int k, double* out_v, int64_t* out_i) {
-    __shared__ double s_v[4];
-    __shared__ int64_t s_i[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    for (int r = 0; r < k; ++r) {
-        double bv = L.v[0];
-        int64_t bi = L.i[0];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(bv, off);
-            const int64_t oi = __shfl_xor(bi, off);
-            if (top_gt(ov, oi, bv, bi)) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        if (lane == 0) {
-            s_v[w] = bv;
-            s_i[w] = bi;
-        }
-        __syncthreads();
-        bv = s_v[0];
-        bi = s_i[0];
-        for (int u = 1; u < (int)(blockDim.x >> 6); ++u)
-            if (top_gt(s_v[u], s_i[u], bv, bi)) {
-                bv = s_v[u];
-                bi = s_i[u];
-            }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            out_v[r] = bv;
-            out_i[r] = bi;
-        }
-        if (bi >= 0 && L.i[0] == bi && L.v[0] == bv) {   // indices are unique: exactly one owner pops
-#pragma unroll
-            for (int p = 0; p + 1 < kTopMax; ++p) {
-                L.v[p] = L.v[p + 1];
-                L.i[p] = L.i[p + 1];
-            }
-            L.v[kTopMax - 1] = -INFINITY;
-            L.i[kTopMax - 1] = -1;
-        }
-    }
-}
-
-// stage 1: block b reduces its contiguous chunk of det[0, n) to k candidates
-__global__ void __launch_bounds__(256) k_top1(const double* __restrict__ det, const int32_t* __restrict__ perm,
-                                              int64_t n, int k, double* pv, int64_t* pi) {
-    const int64_t chunk = (n + gridDim.x - 1) / gridDim.x;
-    const int64_t b0 = (int64_t)blockIdx.x * chunk, b1 = min(n, b0 + chunk);
-    TopList L;
-    L.init();
-    for (int64_t x = b0 + threadIdx.x; x < b1; x += blockDim.x)
-        L.insert(det[x], ((int64_t)perm[x] << 32) | (int64_t)x, k);
-    top_block_emit(L, k, pv + (int64_t)blockIdx.x * k, pi + (int64_t)blockIdx.x * k);
-}
-
-// stage 2: one block merges the m = blocks x k candidates; ascending output (np.argsort(...)[-k:]),
-// plus the matched target index of each winner
-// stage 2: one block reduces the stage-1 candidates; outputs ascending (np.argsort(det)[-k:] order), the
-// source as its original index, the target from the pass's sorted-order record (tgt_sorted)
-__global__ void __launch_bounds__(256) k_top2(const double* pv, const int64_t* pi, int m, int k,
-                                              const int64_t* __restrict__ tgt_sorted, double* ov, int64_t* osrc,
-                                              int64_t* otgt) {
-    __shared__ double s_ov[kTopMax];
-    __shared__ int64_t s_oi[kTopMax];
-    TopList L;
-    L.init();
-    for (int x = threadIdx.x; x < m; x += blockDim.x) L.insert(pv[x], pi[x], k);
-    top_block_emit(L, k, s_ov, s_oi);
-    __syncthreads();
-    if ((int)threadIdx.x < k) {
-        const int r = k - 1 - (int)threadIdx.x;   // descending -> ascending
-        const int64_t si = s_oi[r];
-        ov[threadIdx.x] = si >= 0 ? s_ov[r] : 0.0;
-        osrc[threadIdx.x] = si >= 0 ? (si >> 32) : -1;
-        otgt[threadIdx.x] = si >= 0 ? tgt_sorted[si & 0xFFFFFFFFll] : -1;
-    }
-}
-
-// Each launcher reports hipGetLastError() after its launches.  HIP's last error is per thread and shared
-// with every other HIP user on it (torch, RCCL, the caller): one such user's failed call left there must not
-// fail this library's launch check, so each launcher clears it first.
-static inline void clear_foreign_error() { (void)hipGetLastError(); }
-
-hipError_t launch_top_weights(const double* det, const int64_t* tgt_sorted, const int32_t* perm, int64_t n, int k,
-                              double* scratch_v, int64_t* scratch_i, int blocks, double* ov, int64_t* osrc,
-                              int64_t* otgt, hipStream_t st) {
-    clear_foreign_error();
-    if (k < 1 || k > kTopMax || blocks < 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_top1, dim3(blocks), dim3(256), 0, st, det, perm, n, k, scratch_v, scratch_i);
-    hipLaunchKernelGGL(k_top2, dim3(1), dim3(256), 0, st, scratch_v, scratch_i, blocks * k, k, tgt_sorted, ov, osrc,
-                       otgt);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// rotated covariances (gicp.py:120-121 all_source_cov_matrices): R C Rᵀ = a I − (R m)(R m)ᵀ per
-// point, written in original order.  HBM-bound: 36 B read, D² × 8 B written per point.
-// ---------------------------------------------------------------------------
-struct Rot {
-    double r[9];
-};
-
-template <int D>
-__global__ void __launch_bounds__(256) k_rotate_cov(const double4* __restrict__ cov, const int32_t* __restrict__ perm,
-                                                    int64_t n, Rot R, double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double4 c = cov[i];
-    const double m[3] = {c.y, c.z, c.w};
-    double rm[D];
-#pragma unroll
-    for (int a = 0; a < D; ++a) {
-        double v = 0.0;
-#pragma unroll
-        for (int b = 0; b < D; ++b) v = fma(R.r[a * D + b], m[b], v);
-        rm[a] = v;
-    }
-    double* o = out + (int64_t)perm[i] * D * D;
-#pragma unroll
-    for (int a = 0; a < D; ++a)
-#pragma unroll
-        for (int b = 0; b < D; ++b) o[a * D + b] = (a == b ? c.x : 0.0) - __dmul_rn(rm[a], rm[b]);   // no fma: the
-}                                                                                                 // host formula's rounding
-
-// ---------------------------------------------------------------------------
 // host-side launchers
 // ---------------------------------------------------------------------------
-hipError_t launch_rotate_cov(const double4* cov, const int32_t* perm, int64_t n, int dim, const double* R, double* out,
-                             hipStream_t st) {
-    clear_foreign_error();
-    if (n <= 0) return hipSuccess;
-    Rot r{};
-    for (int k = 0; k < dim * dim; ++k) r.r[k] = R[k];
-    const unsigned g = (unsigned)((n + 255) / 256);
-    if (dim == 2) hipLaunchKernelGGL(k_rotate_cov<2>, dim3(g), dim3(256), 0, st, cov, perm, n, r, out);
-    else hipLaunchKernelGGL(k_rotate_cov<3>, dim3(g), dim3(256), 0, st, cov, perm, n, r, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_morton(const double* xyz, int64_t n, int dim, const DevCloud& fr, uint32_t* codes, int32_t* idx,
-                         hipStream_t st) {
-    clear_foreign_error();
-    const int bs = 256;
-    const unsigned g = (unsigned)((n + bs - 1) / bs);
-    hipLaunchKernelGGL(k_morton, dim3(g), dim3(bs), 0, st, xyz, n, dim, fr, codes, idx);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_tiles(const double* xyz_in, int dim, int32_t* perm, TileInfo* tiles, TileBox* boxes,
-                              int ntiles, double* xyz64, float4* rel32, int32_t* inv, unsigned* rho_bits,
-                              hipStream_t st) {
-    clear_foreign_error();
-    const unsigned g = (unsigned)((ntiles + kWavesPerWG - 1) / kWavesPerWG);
-    hipLaunchKernelGGL(k_build_tiles, dim3(g), dim3(256), 0, st, xyz_in, dim, perm, tiles, boxes, ntiles, xyz64,
-                       rel32, inv, rho_bits);
-    return hipGetLastError();
-}
-
-hipError_t launch_build_blocks(const TileInfo* tiles, int ntiles, BlockInfo* blocks, int nblocks, int dim,
-                               hipStream_t st) {
-    clear_foreign_error();
-    const unsigned g = (unsigned)((nblocks + kWavesPerWG - 1) / kWavesPerWG);
-    hipLaunchKernelGGL(k_build_blocks<TileInfo>, dim3(g), dim3(256), 0, st, tiles, ntiles, blocks, nblocks, dim);
-    const int nsuper = (nblocks + kBlockTiles - 1) / kBlockTiles;   // super-blocks at blocks[nblocks..]
-    const unsigned g2 = (unsigned)((nsuper + kWavesPerWG - 1) / kWavesPerWG);
-    hipLaunchKernelGGL(k_build_blocks<BlockInfo>, dim3(g2), dim3(256), 0, st, (const BlockInfo*)blocks, nblocks,
-                       blocks + nblocks, nsuper, dim);
-    return hipGetLastError();
-}
-
-hipError_t launch_knn_cov(const CovArgs& a, int dim, int k, bool graph, hipStream_t st) {
-    clear_foreign_error();
-    const int nq = a.q_end - a.q_begin;
-    if (nq <= 0) return hipSuccess;
-    if (a.split != 1 && a.split != kSub) return hipErrorInvalidValue;
-    const unsigned g = (unsigned)(((int64_t)nq * a.split + kWavesPerWG - 1) / kWavesPerWG);
-#define GICP_KNN(DD, KK)                                                                              \
-    if (dim == DD && k == KK) {                                                                        \
-        if (graph) hipLaunchKernelGGL((k_knn_cov<DD, KK, true>), dim3(g), dim3(256), 0, st, a);        \
-        else hipLaunchKernelGGL((k_knn_cov<DD, KK, false>), dim3(g), dim3(256), 0, st, a);             \
-        return hipGetLastError();                                                                      \
-    }
-    GICP_KNN(2, 6)
-    GICP_KNN(3, 20)
-    GICP_KNN(3, 10)
-    GICP_KNN(2, 10)
-#undef GICP_KNN
-    return hipErrorInvalidValue;
-}
-
-hipError_t launch_graph_pack(const GraphArgs& a, hipStream_t st) {
-    clear_foreign_error();
-    if (a.cl.n <= 0) return hipSuccess;
-    const unsigned gp = (unsigned)((a.cl.n + 255) / 256);
-    hipLaunchKernelGGL(k_graph_pack, dim3(gp), dim3(256), 0, st, a.nb, a.nbh, a.cl.n, a.nbq, a.nbx, a.nbi);
-    return hipGetLastError();
-}
-
 // Workgroups (units) of a k_corr launch: kCorrWaves source tiles each; with shards, the units of
 // the global chunks shard, shard + nshards, ... (kShardChunk units each, the last one possibly partial).
 int corr_grid(int q_tiles, int shard, int nshards) {
@@ -3104,34 +1687,6 @@ hipError_t launch_corr(const CorrArgs& a, int dim, int grid, hipStream_t st) {
         else hipLaunchKernelGGL((k_corr<3, true>), g, b, 0, st, a);
     } else if (dim == 2) hipLaunchKernelGGL((k_corr<2, false>), g, b, 0, st, a);
     else hipLaunchKernelGGL((k_corr<3, false>), g, b, 0, st, a);
-    return hipGetLastError();
-}
-
-// reset_tile_state's per-source-tile and per-point resets in one launch
-// pose0: slot 0 of the pose ring.  Pass ids restart at 1, so the first pass's "displacement over the last pass"
-// (k_corr disp_since(pass - 1)) reads slot 0, which no pass since the reset has written: it is zeroed here, what a
-// fresh allocation holds, so that the first lists' skin does not depend on what the memory held before.
-__global__ void __launch_bounds__(256) k_reset_tiles(int32_t* hint, int32_t* list_len, float* list_rcert,
-                                                     int32_t* cert_pass, int nt, int32_t* cert_j, int64_t n, double* pose0) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0 && pose0)
-        for (int k = 0; k < 12; ++k) pose0[k] = 0.0;
-    if (i < nt) {
-        hint[i] = -1;
-        list_len[i] = 0;
-        list_rcert[i] = 0.f;
-        if (cert_pass) cert_pass[i] = -1;
-    }
-    if (i < n) cert_j[i] = -1;
-}
-
-hipError_t launch_reset_tiles(int32_t* hint, int32_t* list_len, float* list_rcert, int32_t* cert_pass, int nt,
-                              int32_t* cert_j, int64_t n, double* pose0, hipStream_t st) {
-    clear_foreign_error();
-    const int64_t m = std::max<int64_t>(nt, n);
-    if (m <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_reset_tiles, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, hint, list_len, list_rcert,
-                       cert_pass, nt, cert_j, n, pose0);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // gicp_cov_dev.h — the per-point surface covariance from a neighbourhood's shifted sums (gicp.py:11-35), shared by
-// k_knn_cov (gicp_kernels.hip) and k_batch_cov (gicp_batch.hip): the sums, the smallest eigenvector, the descriptor
+// k_knn_cov (gicp_cov.hip) and k_batch_cov (gicp_batch.hip): the sums, the smallest eigenvector, the descriptor
 // C = a I - m m^T.  Device code only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,7 +28,10 @@ __device__ __forceinline__ void cov_add(CovSums<D>& A, const double* d) {
     }
 }
 
-// Symmetric 3x3 eigenvector of the smallest eigenvalue (cyclic Jacobi, fp64).
+// Symmetric 3x3 eigenvector of the smallest eigenvalue (cyclic Jacobi, fp64).  The sweeps are one text; the
+// eigenvector is picked as V[k][m] with m found at run time, which puts V into a scratch frame (k_knn_cov carries
+// one), or, with Select, by selects over the three columns (k_batch_cov: no scratch).  The same bits either way.
+template <bool Select = false>
 __device__ __forceinline__ void smallest_eigvec3(double A[3][3], double* n) {
     double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
     for (int sweep = 0; sweep < 12; ++sweep) {
@@ -60,14 +63,22 @@ __device__ __forceinline__ void smallest_eigvec3(double A[3][3], double* n) {
             }
         }
     }
-    int m = 0;
-    if (A[1][1] < A[m][m]) m = 1;
-    if (A[2][2] < A[m][m]) m = 2;
-    for (int k = 0; k < 3; ++k) n[k] = V[k][m];
+    if constexpr (Select) {
+        const bool m1 = A[1][1] < A[0][0];
+        const double am = m1 ? A[1][1] : A[0][0];
+        const bool m2 = A[2][2] < am;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) n[k] = m2 ? V[k][2] : (m1 ? V[k][1] : V[k][0]);
+    } else {
+        int m = 0;
+        if (A[1][1] < A[m][m]) m = 1;
+        if (A[2][2] < A[m][m]) m = 2;
+        for (int k = 0; k < 3; ++k) n[k] = V[k][m];
+    }
 }
 
-// C = a I - m m^T from the neighbourhood sums (gicp.py:11-16 / SURVEY.md §8.A)
-template <int D>
+// C = a I - m m^T from the neighbourhood sums (gicp.py:11-16 / SURVEY.md §8.A); Select: smallest_eigvec3's pick
+template <int D, bool Select = false>
 __device__ __forceinline__ double4 cov_descriptor(const CovSums<D>& A, int min_nb, double eps_a, double m_scale) {
     double4 out;
     out.x = 1.0;
@@ -94,7 +105,7 @@ __device__ __forceinline__ double4 cov_descriptor(const CovSums<D>& A, int min_n
         for (int a = 0; a < 3; ++a)
             for (int b = 0; b < 3; ++b) M[a][b] = C[a % D][b % D];
         double nv[3];
-        smallest_eigvec3(M, nv);
+        smallest_eigvec3<Select>(M, nv);
         out.y = nv[0] * m_scale;
         out.z = nv[1] * m_scale;
         out.w = nv[2] * m_scale;

@@ -24,6 +24,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "gicp_bounds_dev.h"
 #include "gicp_filter.h"
 #include "gicp_internal.h"
 
@@ -32,12 +33,6 @@ namespace gicp {
 hipError_t launch_voxel_keys(const VoxelArgs& A, hipStream_t st);   // gicp_voxel.hip
 
 namespace {
-
-// doubles as unsigned integers of the same order (gicp_voxel.hip enc_ordered, gicp_hostmath.cpp dec_ordered)
-__device__ __forceinline__ unsigned long long enc_ordered(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 template <int D>
 __global__ void __launch_bounds__(256) k_crop_flags(CropArgs A) {
@@ -77,12 +72,7 @@ __global__ void __launch_bounds__(256) k_filter_compact(const double* __restrict
     if (i == n - 1) res[6] = (unsigned long long)pos1[i];   // M
     if (__ballot(k) == 0) return;
     for (int a = 0; a < D; ++a) {
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const unsigned long long a0 = __shfl_xor(mn[a], o), a1 = __shfl_xor(mx[a], o);
-            mn[a] = a0 < mn[a] ? a0 : mn[a];
-            mx[a] = a1 > mx[a] ? a1 : mx[a];
-        }
+        GICP_WAVE_BOUNDS(mn[a], mx[a])
         // A wave whose bounds cannot improve the words as it reads them sends no atomic.  The words only ever
         // tighten, so a stale read is a looser bound and costs an atomic it did not need, never a skipped one:
         // without the test every wave's six atomics queue on one line (1M rows: 94k of them, ~1 ms)
@@ -159,8 +149,6 @@ __global__ void __launch_bounds__(256) k_ror_count(VoxelArgs V, RorArgs R) {
     R.keep[o] = count >= R.min_neighbors ? 1 : 0;
     if (Full && R.cnt_out) R.cnt_out[R.idx_in ? R.idx_in[o] : o] = count;
 }
-
-inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 template <int D>
 hipError_t compact(const double* in, int64_t n, int32_t* keep, int32_t* pos1, void* tmp, size_t tmp_bytes,

@@ -443,4 +443,11 @@ constexpr int nstat(int D) {
 constexpr int nstat_ext(int D) { return nstat(D) + 6; }
 static_assert(nstat_ext(3) <= 80, "IterState::stats holds the extended statistics");
 
+// Each launcher reports hipGetLastError() after its launches.  HIP's last error is per thread and shared
+// with every other HIP user on it (torch, RCCL, the caller): one such user's failed call left there must not
+// fail this library's launch check, so each launcher clears it first.
+inline void clear_foreign_error() { (void)hipGetLastError(); }
+// workgroups of 256 threads that cover n rows
+inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
+
 }  // namespace gicp

@@ -10,18 +10,13 @@
 // are the same bits on every call.
 #include <hip/hip_runtime.h>
 
+#include "gicp_bounds_dev.h"
 #include "gicp_internal.h"
 #include "gicp_sweep.h"
 
 namespace gicp {
 
 namespace {
-
-// doubles as unsigned integers of the same order (gicp_voxel.hip enc_ordered, gicp_capi.cpp dec_ordered)
-__device__ __forceinline__ unsigned long long enc_ordered(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __global__ void __launch_bounds__(64) k_deskew_init(unsigned long long* res) {
     if (threadIdx.x < 6) res[threadIdx.x] = threadIdx.x < 3 ? ~0ull : 0ull;
@@ -45,12 +40,7 @@ __global__ void __launch_bounds__(256) k_deskew(SweepArgs A) {
     // (every wave holds a point: the grid is ceil(n / 256) blocks, and waves past n exit here)
     if (__ballot(in) == 0) return;
     for (int a = 0; a < D; ++a) {
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const unsigned long long a0 = __shfl_xor(mn[a], o), a1 = __shfl_xor(mx[a], o);
-            mn[a] = a0 < mn[a] ? a0 : mn[a];
-            mx[a] = a1 > mx[a] ? a1 : mx[a];
-        }
+        GICP_WAVE_BOUNDS(mn[a], mx[a])
         if ((threadIdx.x & 63) == 0) {
             atomicMin(&A.res[a], mn[a]);
             atomicMax(&A.res[3 + a], mx[a]);
@@ -62,9 +52,9 @@ __global__ void __launch_bounds__(256) k_deskew(SweepArgs A) {
 
 // De-skew A.pts [n][dim] in place on `st`; A.res[0..5] receive the ordered-integer bounds of the result.
 hipError_t launch_deskew(const SweepArgs& A, hipStream_t st) {
-    (void)hipGetLastError();
+    clear_foreign_error();
     if (A.n <= 0 || (A.dim != 2 && A.dim != 3) || !A.pts || !A.stamps || !A.res) return hipErrorInvalidValue;
-    const unsigned g = (unsigned)((A.n + 255) / 256);
+    const unsigned g = grid256(A.n);
     hipLaunchKernelGGL(k_deskew_init, dim3(1), dim3(64), 0, st, A.res);
     if (A.dim == 3) hipLaunchKernelGGL(k_deskew<3>, dim3(g), dim3(256), 0, st, A);
     else hipLaunchKernelGGL(k_deskew<2>, dim3(g), dim3(256), 0, st, A);

@@ -26,18 +26,12 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "gicp_bounds_dev.h"
 #include "gicp_internal.h"
 
 namespace gicp {
 
 namespace {
-
-// doubles as unsigned integers of the same order (-0.0 < +0.0): min / max by integer atomics are exact and
-// independent of the order of arrival
-__device__ __forceinline__ unsigned long long enc_ordered(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
 
 __global__ void __launch_bounds__(256) k_voxel_key(VoxelArgs A) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -208,12 +202,7 @@ __global__ void __launch_bounds__(256) k_voxel_compact(VoxelArgs A, const int32_
     }
     if (__ballot(k) == 0) return;
     for (int a = 0; a < A.dim; ++a) {
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const unsigned long long a0 = __shfl_xor(mn[a], o), a1 = __shfl_xor(mx[a], o);
-            mn[a] = a0 < mn[a] ? a0 : mn[a];
-            mx[a] = a1 > mx[a] ? a1 : mx[a];
-        }
+        GICP_WAVE_BOUNDS(mn[a], mx[a])
         if ((threadIdx.x & 63) == 0) {
             atomicMin(&A.res[a], mn[a]);
             atomicMax(&A.res[3 + a], mx[a]);
@@ -323,20 +312,13 @@ __global__ void __launch_bounds__(256) k_map_centroids(const double* __restrict_
     if (v == m - 1) res[6] = (unsigned long long)pos1[v];
     if (__ballot(k) == 0) return;
     for (int a = 0; a < dim; ++a) {
-#pragma unroll
-        for (int o = 1; o < kWave; o <<= 1) {
-            const unsigned long long a0 = __shfl_xor(mn[a], o), a1 = __shfl_xor(mx[a], o);
-            mn[a] = a0 < mn[a] ? a0 : mn[a];
-            mx[a] = a1 > mx[a] ? a1 : mx[a];
-        }
+        GICP_WAVE_BOUNDS(mn[a], mx[a])
         if ((threadIdx.x & 63) == 0) {
             atomicMin(&res[a], mn[a]);
             atomicMax(&res[3 + a], mx[a]);
         }
     }
 }
-
-inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 

@@ -283,12 +283,14 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, _DP, C.c_int, C.c_void_p)
 _lib = None
 
 # the sources gicp_build_info()'s hash covers, in the Makefile's HASH_SRCS order
-HASH_SRCS = ("csrc/gicp_kernels.hip", "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
+HASH_SRCS = ("csrc/gicp_index.hip", "csrc/gicp_cov.hip", "csrc/gicp_corr.hip", "csrc/gicp_extras.hip",
+             "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
              "csrc/gicp_build.cpp", "csrc/gicp_align.cpp", "csrc/gicp_exchange.cpp", "csrc/gicp_voxel.hip",
              "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_filter.hip", "csrc/gicp_batch.hip", "csrc/gicp_batch.cpp",
              "csrc/gicp_internal.h", "csrc/gicp_mem.h",
              "csrc/gicp_sweep.h", "csrc/gicp_filter.h", "csrc/gicp_cov_dev.h", "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
-             "../include/gicp_hip.h")
+             "../include/gicp_hip.h",
+             "csrc/gicp_wave_dev.h", "csrc/gicp_search_dev.h", "csrc/gicp_stats_dev.h", "csrc/gicp_bounds_dev.h")
 
 
 def source_hash():

@@ -205,11 +205,12 @@ int gicp_peer_init(gicp_ctx* ctx, int nranks, int rank, const char* handles, dou
 int gicp_peer_close(gicp_ctx* ctx);   /* back to no exchange (RCCL / hook as set before are dropped by init) */
 
 /* Build provenance of this library: "src=<first 16 hex of sha256 over the sources>;git=<rev>;built=<date
- * time>;arch=gfx950".  The source hash covers csrc/{gicp_kernels.hip, gicp_capi.cpp, gicp_solver.cpp,
- * gicp_cg.cpp, gicp_hostmath.cpp, gicp_build.cpp, gicp_align.cpp, gicp_exchange.cpp, gicp_voxel.hip, gicp_sweep.hip,
- * gicp_eval.hip, gicp_filter.hip, gicp_batch.hip, gicp_batch.cpp, gicp_internal.h, gicp_mem.h, gicp_sweep.h,
- * gicp_filter.h, gicp_cov_dev.h, gicp_solver.h, gicp_solve_dev.h, gicp_hostmath.h, gicp_host.h} and
- * include/gicp_hip.h, concatenated in that order, so
+ * time>;arch=gfx950".  The source hash covers csrc/{gicp_index.hip, gicp_cov.hip, gicp_corr.hip, gicp_extras.hip,
+ * gicp_capi.cpp, gicp_solver.cpp, gicp_cg.cpp, gicp_hostmath.cpp, gicp_build.cpp, gicp_align.cpp, gicp_exchange.cpp,
+ * gicp_voxel.hip, gicp_sweep.hip, gicp_eval.hip, gicp_filter.hip, gicp_batch.hip, gicp_batch.cpp, gicp_internal.h,
+ * gicp_mem.h, gicp_sweep.h, gicp_filter.h, gicp_cov_dev.h, gicp_solver.h, gicp_solve_dev.h, gicp_hostmath.h,
+ * gicp_host.h}, include/gicp_hip.h and csrc/{gicp_wave_dev.h, gicp_search_dev.h, gicp_stats_dev.h,
+ * gicp_bounds_dev.h}, concatenated in that order (the Makefile's SRCS, then its HEADERS), so
  * a caller can prove the loaded library was compiled from the sources beside it. */
 const char* gicp_build_info(void);
 

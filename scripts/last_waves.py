@@ -5,7 +5,7 @@
 
 The bench's clouds, a cold registration from the identity: pass k runs at the pose the solve of pass k-1 gave
 (gicp_iterate + the host solve, the sequence gicp_align runs), each launch's per-wave record dumped by the
-timeline build (gicp_kernels.hip GICP_TIMELINE: wave start and end, the end of its certificate + descent
+timeline build (gicp_corr.hip GICP_TIMELINE: wave start and end, the end of its certificate + descent
 phase, the end of its walk, the walk's kind, lanes that descended / walked, tile visits, tiles scanned, list
 use, block tests).  Per pass it prints the span and, for the last 1 % of waves to finish (and the last 10),
 what they did: the phase that took their time, the walk's kind, visits, walking lanes, start time.

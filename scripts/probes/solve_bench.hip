@@ -28,7 +28,7 @@ __device__ unsigned long long* g_stamp_out;
         }                                                                                    \
     } while (0)
 #endif
-#include "gicp_kernels.hip"
+#include "gicp_corr.hip"
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
 

@@ -40,6 +40,18 @@ def test_build_info_matches_the_sources_in_this_tree():
     assert info["src"] == _lib.source_hash(), (info, "rebuild: make -C generalized-icp_amd/csrc")
 
 
+def test_hash_sources_are_the_makefiles_sources_then_headers():
+    """source_hash() reads the files the Makefile hashes, in its order: SRCS, then HEADERS."""
+    mk = open(os.path.join(ROOT, "generalized-icp_amd", "csrc", "Makefile")).read()
+    var = {k: re.search(rf"^{k} = (.*)$", mk, flags=re.M).group(1).split() for k in ("SRCS", "HEADERS")}
+    assert re.search(r"^HASH_SRCS = \$\(SRCS\) \$\(HEADERS\)$", mk, flags=re.M)
+    want = [os.path.normpath(os.path.join("csrc", f)) for f in var["SRCS"] + var["HEADERS"]]
+    assert len(want) > 20 and len(set(want)) == len(want)
+    assert [os.path.normpath(f) for f in _lib.HASH_SRCS] == want
+    for f in _lib.HASH_SRCS:
+        assert os.path.isfile(os.path.join(ROOT, "generalized-icp_amd", f)), f
+
+
 def test_basic_host_entry_points():
     lib = _lib.load()
     assert lib.gicp_version() >= 100

@@ -384,9 +384,9 @@ void evaluate(gicp_ctx* c, const double* T, const gicp_params* p, const gicp_rep
         a.idx = c->d_dbg_idx;
         a.dist = c->d_dbg_dist;
         a.w = c->d_dbg_w;
-        a.src_xyz = c->src.xyz64;
+        a.src_xyz = c->src.rec;
         a.src_inv = c->src.inv;
-        a.tgt_xyz = c->tgt.xyz64;
+        a.tgt_xyz = c->tgt.rec;
         a.tgt_inv = c->tgt.inv;
         a.n = c->src.n;
         a.m = c->tgt.n;

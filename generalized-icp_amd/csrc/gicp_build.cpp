@@ -299,7 +299,7 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
     cl.seed_shift = build_seed_table(tcode, dim * cl.bits, seed);
     cl.seed_tab.reserve(seed.size());
     HIPCHK(hipMemcpyAsync(cl.seed_tab, seed.data(), sizeof(int32_t) * seed.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(launch_build_tiles(d_in, dim, cl.perm, cl.tiles, cl.boxes, cl.ntiles, cl.xyz64, cl.rel32, cl.inv, d_rho, st));
+    HIPCHK(launch_build_tiles(d_in, dim, cl.perm, cl.tiles, cl.boxes, cl.ntiles, cl.rec, cl.rel32, cl.inv, d_rho, st));
     HIPCHK(launch_build_blocks(cl.tiles, cl.ntiles, cl.blocks, cl.nblocks, dim, st));
     unsigned rho_bits = 0;
     HIPCHK(hipMemcpyAsync(&rho_bits, d_rho, sizeof(unsigned), hipMemcpyDeviceToHost, st));
@@ -309,13 +309,14 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
 
     // surface covariances (gicp.py:19-35), of this rank's tiles when sharded
     const int qb = 0, qe = shard_tile_count(cl.ntiles, spec.cov_shard, spec.cov_nshards);
+    cl.eps_a = p.epsilon;   // remembered by the cloud: its records do not store a
     CovArgs ca{};
     ca.cl = cl.view();
     ca.q_begin = qb;
     ca.q_end = qe;
     ca.sh_n = spec.cov_nshards;
     ca.sh_r = spec.cov_shard;
-    if (spec.cov_nshards > 1) HIPCHK(hipMemsetAsync(cl.cov, 0xFF, sizeof(double4) * n, st));   // NaN: not computed
+    // (every record's m was marked "not computed" by k_build_tiles: the rows of another shard stay so)
     const double dn = p.max_distance_nearest_neighbors;
     ca.mg = make_margin(dim, cl.rho, cl.rho, dn);
     ca.search2 = screen_bound(ca.mg, dn);
@@ -323,7 +324,7 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
     ca.eps_a = p.epsilon;
     ca.m_scale = std::sqrt(p.epsilon * (1.0 - p.ratio));
     ca.min_nb = p.min_neighbors;
-    ca.cov_out = cl.cov;
+    ca.rec_out = cl.rec;
     ca.count_out = cl.ncount;
     ca.amb_counter = bs.d_amb;
     // waves per query tile: a synchronous build of a small cloud is split by sub-tile (the walk of its
@@ -548,7 +549,7 @@ void copy_covariances(gicp_ctx* c, Cloud& cl, const double* R, double* out) {
     const int d = cl.dim;
     const size_t m = (size_t)cl.n * d * d;
     c->d_rot.reserve(m);
-    HIPCHK(launch_rotate_cov(cl.cov, cl.perm, cl.n, d, R, c->d_rot, c->stream));
+    HIPCHK(launch_rotate_cov(cl.rec, cl.eps_a, cl.perm, cl.n, d, R, c->d_rot, c->stream));
     HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
 }
@@ -556,7 +557,7 @@ void copy_covariances(gicp_ctx* c, Cloud& cl, const double* R, double* out) {
 void copy_points(gicp_ctx* c, Cloud& cl, double* out) {
     const size_t m = (size_t)cl.n * cl.dim;
     c->d_rot.reserve(m);
-    HIPCHK(launch_points_out(cl.xyz64, cl.perm, cl.n, cl.dim, c->d_rot, c->stream));
+    HIPCHK(launch_points_out(cl.rec, cl.perm, cl.n, cl.dim, c->d_rot, c->stream));
     HIPCHK(hipMemcpyAsync(out, c->d_rot, sizeof(double) * m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
 }
@@ -635,7 +636,7 @@ void deskew_cloud(gicp_ctx* c, const double* xyz, const double* stamps, int64_t 
 void map_insert(gicp_ctx* c, const Cloud* cl, const double* xyz, int64_t n, const double* T) {
     VoxelMap& mp = c->map;
     mp.pts.reserve((size_t)n * mp.dim);
-    if (cl) HIPCHK(launch_points_out(cl->xyz64, cl->perm, cl->n, cl->dim, mp.pts, c->stream));
+    if (cl) HIPCHK(launch_points_out(cl->rec, cl->perm, cl->n, cl->dim, mp.pts, c->stream));
     else HIPCHK(hipMemcpyAsync(mp.pts, xyz, sizeof(double) * n * mp.dim, hipMemcpyHostToDevice, c->stream));
     map_insert_core(mp, c->bs, n, T, c->stream);
 }

@@ -352,7 +352,9 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
         float qr[3] = {0.f, 0.f, 0.f}, d2jp = 0.f;
         uint32_t w0[16];   // the first half of jp's graph row (the descent's first step), requested with jp
         if (A.cert_j && q.valid && !cert && jp >= 0 && jp < tg.n) {
-            const double4 t4 = reinterpret_cast<const double4*>(tg.xyz64)[jp];
+            // (the first 32 B of jp's record: its position)
+            const double2* const tp = reinterpret_cast<const double2*>(tg.rec + jp);
+            const double2 t01 = tp[0], t23 = tp[1];
             if (tg.nbq) {
                 const uint4* row = tg.nbq + (int64_t)jp * 8;
 #pragma unroll
@@ -364,7 +366,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
                     w0[4 * c + 3] = v.w;
                 }
             }
-            const double tv[3] = {t4.x, t4.y, t4.z};
+            const double tv[3] = {t01.x, t01.y, t23.x};
 #pragma unroll
             for (int a = 0; a < D; ++a) {
                 qr[a] = (float)(q.ow[a] - tv[a]) + q.pw[a];
@@ -573,7 +575,10 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
                 if (tie) {
                     double p64[D];
                     {
-                        const double4 s4 = reinterpret_cast<const double4*>(A.src.xyz64)[i];
+                        // (record i's address formed as i x 32 B + i x 16 B: as one multiply by 48 it cost the 2-D
+                        // kernel 4 VGPRs and 32 B of scratch at the descent's register peak)
+                        const double* sq = reinterpret_cast<const double*>(A.src.rec) + (int64_t)i * 4;
+                        const RecPos s4 = rec_pos(reinterpret_cast<const PointRec*>(sq + (int64_t)i * 2));
                         const double s4v[3] = {s4.x, s4.y, s4.z};
 #pragma unroll
                         for (int a = 0; a < D; ++a) {
@@ -586,7 +591,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
                     double bd2 = 1e300, sd2 = 1e300;
                     int bj = -1, bo = 0x7fffffff;
                     auto consider = [&](int t) {
-                        const double4 t4 = reinterpret_cast<const double4*>(tg.xyz64)[t];
+                        const RecPos t4 = rec_pos(tg.rec + t);
                         const double tv[3] = {t4.x, t4.y, t4.z};
                         const double d2 = dist2_exact<D>(tv, p64);
                         const int og = tg.perm[t];
@@ -1006,8 +1011,8 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
         // matches and covariances in the epilogue: one memory round trip instead of two
         // the transformed point q.p64 (the untransformed one, sv, a statistics term, is set from the epilogue's
         // own request of the point: held from here it was spilled through the fp64 re-resolution)
-        auto source_point = [&](const double4& s4) {
-            const double s4v[3] = {s4.x, s4.y, s4.z};
+        auto source_point = [&](double sx, double sy, double sz) {
+            const double s4v[3] = {sx, sy, sz};
 #pragma unroll
             for (int a = 0; a < D; ++a) {
                 double p = P.t[a];
@@ -1017,7 +1022,10 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
             }
         };
         refresh_i();
-        if (!skip_walk) source_point(reinterpret_cast<const double4*>(sc.xyz64)[i]);
+        if (!skip_walk) {
+            const RecPos s4 = rec_pos(sc.rec + i);
+            source_point(s4.x, s4.y, s4.z);
+        }
         const bool found = cert ? cj >= 0 : (q.valid && best < init);
         int j = -1;
         double d2e = 0.0;
@@ -1140,7 +1148,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
                             double d2 = 1e300;
                             int og = 0x7fffffff;
                             if (l < c0) {
-                                const double4 x = reinterpret_cast<const double4*>(tg.xyz64)[s0 + l];
+                                const RecPos x = rec_pos(tg.rec + (s0 + l));
                                 og = tg.perm[s0 + l];
                                 const double xv[3] = {x.x, x.y, x.z};
                                 d2 = dist2_exact<D>(xv, pa);
@@ -1226,27 +1234,46 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
 
         S.mark(4);
         // ---- epilogue: distance check, W = inv(R C_s R^T + C_t), statistics --
-        const double4 s4e = reinterpret_cast<const double4*>(sc.xyz64)[i];
-        sv[0] = s4e.x;
-        sv[1] = s4e.y;
-        if (D == 3) sv[D - 1] = s4e.z;
+        // the source's record: its position now (sv, a statistics term, for every lane) ...
+        const PointRec* const sr = sc.rec + i;
+        const double2 sxy = *reinterpret_cast<const double2*>(sr);
+        double2 szm = make_double2(0.0, 0.0);   // (z, m0); 2-D: z = 0, m0 requested below
+        if constexpr (D == 3) szm = reinterpret_cast<const double2*>(sr)[1];
+        sv[0] = sxy.x;
+        sv[1] = sxy.y;
+        if (D == 3) sv[D - 1] = szm.x;
         if (found && j >= 0) {
-            // match position and both covariances requested together (one memory round trip)
-            const double4 q4 = reinterpret_cast<const double4*>(tg.xyz64)[j];
-            const double4 ct = tg.cov[j];
-            const double4 cs = sc.cov[i];
-            if (skip_walk) source_point(s4e);
-            const double qv[3] = {q4.x, q4.y, q4.z};
+            // ... and its m with the match's record, requested together (one memory round trip).  3-D: the
+            // three 16-B words of each record; 2-D: z and m2 are 0 and not read (x y, then m0 and m1)
+            const PointRec* const tr = tg.rec + j;
+            const double2 txy = *reinterpret_cast<const double2*>(tr);
+            double2 tzm = make_double2(0.0, 0.0), tmm = make_double2(0.0, 0.0), smm = make_double2(0.0, 0.0);
+            if constexpr (D == 3) {
+                tzm = reinterpret_cast<const double2*>(tr)[1];
+                tmm = reinterpret_cast<const double2*>(tr)[2];
+                smm = reinterpret_cast<const double2*>(sr)[2];
+            } else {
+                tzm.y = tr->m0;
+                tmm.x = tr->m1;
+                szm.y = sr->m0;
+                smm.x = sr->m1;
+            }
+            if (skip_walk) source_point(sxy.x, sxy.y, szm.x);
+            const double qv[3] = {txy.x, txy.y, tzm.x};
+            // a of both covariances and the marked rows' m0 (decode_cov: a is not stored)
+            double as_, at_, ms0, mt0;
+            decode_cov(sc.eps_a, szm.y, smm.x, as_, ms0);
+            decode_cov(tg.eps_a, tzm.y, tmm.x, at_, mt0);
             d2e = dist2_exact<D>(qv, q.p64);
 #ifdef GICP_TIMELINE
-            S.te = tl_after(d2e, ct.x + cs.x);   // the epilogue's gathers are in
+            S.te = tl_after(d2e, at_ + as_);   // the epilogue's gathers are in
 #endif
             if (A.dbg_dist) A.dbg_dist[sc.perm[i]] = sqrt(d2e);
             // gicp.py:136: reject only if distance > d_c; sqrt(d2) > d_c <=> d2 > dc2_max (host-computed,
             // sqrt is correctly rounded and monotone), so no square root here
             if (d2e <= A.dc2_max) {
                 on = true;
-                const double mt[3] = {ct.y, ct.z, ct.w};
+                const double mt[3] = {mt0, tmm.x, tmm.y};
                 if (A.cov_model == GICP_COV_POINT_TO_POINT) {          // C_s = 0, C_t = I: W = I
 #pragma unroll
                     for (int a = 0; a < D; ++a)
@@ -1258,7 +1285,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
 #pragma unroll
                         for (int b = 0; b < D; ++b) W[a][b] = mt[a] * mt[b] * A.pl_inv;
                 } else {
-                const double ms[3] = {cs.y, cs.z, cs.w};
+                const double ms[3] = {ms0, smm.x, smm.y};
                 double mr[D];
 #pragma unroll
                 for (int a = 0; a < D; ++a) {
@@ -1271,7 +1298,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
                 for (int a = 0; a < D; ++a)
 #pragma unroll
                     for (int b = 0; b < D; ++b)
-                        S[a][b] = (a == b ? cs.x + ct.x : 0.0) - mr[a] * mr[b] - mt[a] * mt[b];
+                        S[a][b] = (a == b ? as_ + at_ : 0.0) - mr[a] * mr[b] - mt[a] * mt[b];
                 if constexpr (D == 2) {
                     const double det = S[0][0] * S[1][1] - S[0][1] * S[1][0];
                     const double id = solver_detail::recip(det);
@@ -1337,7 +1364,7 @@ __global__ void __launch_bounds__(64 * kCorrWaves) GICP_CORR_ATTR k_corr(CorrArg
             }
             if (A.dbg_index) A.dbg_index[sc.perm[i]] = on ? (int64_t)tg.perm[j] : -1;
         } else if (q.valid) {
-            if (skip_walk) source_point(s4e);
+            if (skip_walk) source_point(sxy.x, sxy.y, szm.x);
             if (A.dbg_index) A.dbg_index[sc.perm[i]] = -1;
             if (A.dbg_dist) A.dbg_dist[sc.perm[i]] = 1.0 / 0.0;
         }

@@ -224,7 +224,13 @@ __global__ void __launch_bounds__(256) k_knn_cov(CovArgs A) {
     }
 
     if (q.valid) {
-        A.cov_out[i] = cov_descriptor<D>(S, A.min_nb, A.eps_a, A.m_scale);
+        // m into the point's record (PointRec: a is the cloud's epsilon and is not stored; an isolated point,
+        // the descriptor's own test, is marked in m0)
+        const double4 cd = cov_descriptor<D>(S, A.min_nb, A.eps_a, A.m_scale);
+        const bool isolated = S.n < (double)A.min_nb;
+        PointRec* const r = A.rec_out + i;
+        r->m0 = isolated ? __longlong_as_double((long long)kRecIsolated) : cd.y;
+        *reinterpret_cast<double2*>(&r->m1) = make_double2(cd.z, cd.w);
         A.count_out[i] = (int)S.n;
     }
 }

@@ -69,10 +69,10 @@ __global__ void __launch_bounds__(kEvalBlock) k_eval_values(EvalArgs A) {
         dist = A.dist[i];
     }
     const bool acc = in && j >= 0 && j < A.m;
-    double4 s4 = {0.0, 0.0, 0.0, 0.0}, q4 = {0.0, 0.0, 0.0, 0.0};
+    RecPos s4 = {0.0, 0.0, 0.0}, q4 = {0.0, 0.0, 0.0};
     if (acc) {
-        s4 = reinterpret_cast<const double4*>(A.src_xyz)[A.src_inv[i]];
-        q4 = reinterpret_cast<const double4*>(A.tgt_xyz)[A.tgt_inv[j]];
+        s4 = rec_pos(A.src_xyz + A.src_inv[i]);
+        q4 = rec_pos(A.tgt_xyz + A.tgt_inv[j]);
     }
     __syncthreads();
     unsigned long long kd = ~0ull, ks = ~0ull;

@@ -138,19 +138,23 @@ hipError_t launch_top_weights(const double* det, const int64_t* tgt_sorted, cons
 
 // ---------------------------------------------------------------------------
 // rotated covariances (gicp.py:120-121 all_source_cov_matrices): R C Rᵀ = a I − (R m)(R m)ᵀ per
-// point, written in original order.  HBM-bound: 36 B read, D² × 8 B written per point.
+// point, written in original order, a and m decoded from the point records (decode_cov; a row that was not
+// computed comes out NaN).  HBM-bound: 52 B read, D² × 8 B written per point.
 // ---------------------------------------------------------------------------
 struct Rot {
     double r[9];
 };
 
 template <int D>
-__global__ void __launch_bounds__(256) k_rotate_cov(const double4* __restrict__ cov, const int32_t* __restrict__ perm,
-                                                    int64_t n, Rot R, double* __restrict__ out) {
+__global__ void __launch_bounds__(256) k_rotate_cov(const PointRec* __restrict__ rec, double eps_a,
+                                                    const int32_t* __restrict__ perm, int64_t n, Rot R,
+                                                    double* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double4 c = cov[i];
-    const double m[3] = {c.y, c.z, c.w};
+    const double s0 = rec[i].m0, s1 = rec[i].m1, s2 = rec[i].m2;
+    double ca, m0;
+    decode_cov(eps_a, s0, s1, ca, m0);
+    const double m[3] = {m0, s1, s2};
     double rm[D];
 #pragma unroll
     for (int a = 0; a < D; ++a) {
@@ -163,18 +167,18 @@ __global__ void __launch_bounds__(256) k_rotate_cov(const double4* __restrict__ 
 #pragma unroll
     for (int a = 0; a < D; ++a)
 #pragma unroll
-        for (int b = 0; b < D; ++b) o[a * D + b] = (a == b ? c.x : 0.0) - __dmul_rn(rm[a], rm[b]);   // no fma: the
+        for (int b = 0; b < D; ++b) o[a * D + b] = (a == b ? ca : 0.0) - __dmul_rn(rm[a], rm[b]);   // no fma: the
 }                                                                                                 // host formula's rounding
 
-hipError_t launch_rotate_cov(const double4* cov, const int32_t* perm, int64_t n, int dim, const double* R, double* out,
-                             hipStream_t st) {
+hipError_t launch_rotate_cov(const PointRec* rec, double eps_a, const int32_t* perm, int64_t n, int dim, const double* R,
+                             double* out, hipStream_t st) {
     clear_foreign_error();
     if (n <= 0) return hipSuccess;
     Rot r{};
     for (int k = 0; k < dim * dim; ++k) r.r[k] = R[k];
     const unsigned g = grid256(n);
-    if (dim == 2) hipLaunchKernelGGL(k_rotate_cov<2>, dim3(g), dim3(256), 0, st, cov, perm, n, r, out);
-    else hipLaunchKernelGGL(k_rotate_cov<3>, dim3(g), dim3(256), 0, st, cov, perm, n, r, out);
+    if (dim == 2) hipLaunchKernelGGL(k_rotate_cov<2>, dim3(g), dim3(256), 0, st, rec, eps_a, perm, n, r, out);
+    else hipLaunchKernelGGL(k_rotate_cov<3>, dim3(g), dim3(256), 0, st, rec, eps_a, perm, n, r, out);
     return hipGetLastError();
 }
 

@@ -19,7 +19,7 @@
 
 namespace gicp {
 hipError_t launch_morton(const double*, int64_t, int, const DevCloud&, uint32_t*, int32_t*, hipStream_t);
-hipError_t launch_build_tiles(const double*, int, int32_t*, TileInfo*, TileBox*, int, double*, float4*, int32_t*,
+hipError_t launch_build_tiles(const double*, int, int32_t*, TileInfo*, TileBox*, int, PointRec*, float4*, int32_t*,
                               unsigned*, hipStream_t);
 hipError_t launch_build_blocks(const TileInfo*, int, BlockInfo*, int, int, hipStream_t);
 hipError_t launch_knn_cov(const CovArgs&, int, int, bool, hipStream_t);
@@ -28,14 +28,14 @@ hipError_t launch_solve(IterState*, int, hipStream_t, double*);
 hipError_t launch_peer_probe(const PeerArgs&, double*, hipStream_t);
 hipError_t launch_reset_tiles(int32_t*, int32_t*, float*, int32_t*, int, int32_t*, int64_t, double*, hipStream_t);
 hipError_t launch_graph_pack(const GraphArgs&, hipStream_t);
-hipError_t launch_rotate_cov(const double4*, const int32_t*, int64_t, int, const double*, double*, hipStream_t);
+hipError_t launch_rotate_cov(const PointRec*, double, const int32_t*, int64_t, int, const double*, double*, hipStream_t);
 hipError_t launch_top_weights(const double*, const int64_t*, const int32_t*, int64_t, int, double*, int64_t*, int, double*, int64_t*,
                               int64_t*, hipStream_t);
 hipError_t voxel_temp_bytes(int64_t, int, size_t*, hipStream_t);
 hipError_t launch_voxel(const VoxelArgs&, hipStream_t);
 hipError_t launch_crop(const CropArgs&, hipStream_t);
 hipError_t launch_ror(const VoxelArgs&, const RorArgs&, hipStream_t);
-hipError_t launch_points_out(const double*, const int32_t*, int64_t, int, double*, hipStream_t);
+hipError_t launch_points_out(const PointRec*, const int32_t*, int64_t, int, double*, hipStream_t);
 hipError_t launch_deskew(const SweepArgs&, hipStream_t);
 hipError_t launch_eval(const EvalArgs&, hipStream_t);
 hipError_t launch_map_insert(const VoxelArgs&, const MapArgs&, hipStream_t);
@@ -71,11 +71,13 @@ struct Cloud {
     double lo[3] = {0, 0, 0};
     double scale = 1.0;
     float rho = 0.f;
+    // the epsilon the cloud was built with (a of C = a I - m m^T for every surface point, DevCloud::eps_a): it
+    // belongs to the cloud, not to the context's current parameters, and moves with it through every swap
+    double eps_a = 0.0;
     // the buffers are grow-only and move with the cloud: a swap of two clouds swaps them, and the side that
     // is then cleared (n = 0) keeps its buffers as spares for the next build
-    DevBuf<double> xyz64;
+    DevBuf<PointRec> rec;             // positions and covariances, one 48-B record per point
     DevBuf<float4> rel32;
-    DevBuf<double4> cov;
     DevBuf<int32_t> perm, inv, ncount;
     DevBuf<TileInfo> tiles;
     DevBuf<BlockInfo> blocks;
@@ -97,9 +99,8 @@ struct Cloud {
         graph_ready = false;
     }
     void reserve_points(int64_t np) {
-        xyz64.reserve((size_t)np * 4);
+        rec.reserve((size_t)np);
         rel32.reserve((size_t)np);
-        cov.reserve((size_t)np);
         perm.reserve((size_t)np);
         inv.reserve((size_t)np);
         ncount.reserve((size_t)np);
@@ -112,9 +113,9 @@ struct Cloud {
     }
     DevCloud view() const {
         DevCloud v{};
-        v.xyz64 = xyz64;
+        v.rec = rec;
         v.rel32 = rel32;
-        v.cov = cov;
+        v.eps_a = eps_a;
         v.perm = perm;
         v.tiles = tiles;
         v.blocks = blocks;

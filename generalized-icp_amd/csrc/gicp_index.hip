@@ -62,7 +62,7 @@ __device__ __forceinline__ void split_order(double (&p)[3], int& o, int dim, boo
 
 __global__ void __launch_bounds__(256) k_build_tiles(const double* __restrict__ xyz_in, int dim,
                                                       int32_t* __restrict__ perm, TileInfo* tiles, TileBox* boxes,
-                                                      int ntiles, double* xyz64, float4* rel32, int32_t* inv,
+                                                      int ntiles, PointRec* rec, float4* rel32, int32_t* inv,
                                                       unsigned* rho_bits) {
     const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
     const int T = blockIdx.x * kWavesPerWG + w;
@@ -80,12 +80,13 @@ __global__ void __launch_bounds__(256) k_build_tiles(const double* __restrict__ 
     if (v) {
         perm[i] = o;
         inv[o] = i;
-        double4 q;
-        q.x = p[0];
-        q.y = p[1];
-        q.z = p[2];
-        q.w = 0.0;
-        reinterpret_cast<double4*>(xyz64)[i] = q;
+        // the point's record: its position, and m marked "not computed" until k_knn_cov writes it (a sharded
+        // build computes the covariances of its own tiles only, gicp_get_covariances reads the others as NaN)
+        const double nc = __longlong_as_double((long long)kRecNotComputed);
+        double2* const r2 = reinterpret_cast<double2*>(rec + i);
+        r2[0] = make_double2(p[0], p[1]);
+        r2[1] = make_double2(p[2], nc);
+        r2[2] = make_double2(nc, nc);
     }
     double c[3];
     for (int a = 0; a < 3; ++a) {
@@ -201,11 +202,11 @@ hipError_t launch_morton(const double* xyz, int64_t n, int dim, const DevCloud& 
 }
 
 hipError_t launch_build_tiles(const double* xyz_in, int dim, int32_t* perm, TileInfo* tiles, TileBox* boxes,
-                              int ntiles, double* xyz64, float4* rel32, int32_t* inv, unsigned* rho_bits,
+                              int ntiles, PointRec* rec, float4* rel32, int32_t* inv, unsigned* rho_bits,
                               hipStream_t st) {
     clear_foreign_error();
     const unsigned g = (unsigned)((ntiles + kWavesPerWG - 1) / kWavesPerWG);
-    hipLaunchKernelGGL(k_build_tiles, dim3(g), dim3(256), 0, st, xyz_in, dim, perm, tiles, boxes, ntiles, xyz64,
+    hipLaunchKernelGGL(k_build_tiles, dim3(g), dim3(256), 0, st, xyz_in, dim, perm, tiles, boxes, ntiles, rec,
                        rel32, inv, rho_bits);
     return hipGetLastError();
 }

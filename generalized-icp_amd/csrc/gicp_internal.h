@@ -79,11 +79,25 @@ struct __attribute__((aligned(16))) BlockInfo {
     float pad;
 };
 
+// One point of an indexed cloud: its fp64 position and the m of its covariance C = a I - m m^T, 48 B, so a
+// record is three 16-B loads (16-B aligned; two of every three records straddle a 128-B line).  In 2-D z = m2 = 0.
+// `a` is not stored: it is the cloud's epsilon (DevCloud::eps_a) for a point with a surface covariance and 1 for
+// an isolated one (C = I, m = 0), which m0 marks with kRecIsolated; a row whose covariance was not computed (another
+// shard's) has every bit of m set (kRecNotComputed) and decodes as NaN.  Both marks are NaNs, which no computed m0
+// is, so "m0 is a NaN" tells a marked row (decode_cov); a surface point with m = 0 (ratio = 1) is not marked.
+struct __attribute__((aligned(16))) PointRec {
+    double x, y, z;
+    double m0, m1, m2;
+};
+static_assert(sizeof(PointRec) == 48, "a point record is three 16-B words");
+constexpr unsigned long long kRecIsolated = 0x7FF8000000000001ull;      // m0 of an isolated point (m1 = m2 = +0)
+constexpr unsigned long long kRecNotComputed = 0xFFFFFFFFFFFFFFFFull;   // m0, m1, m2 of a row that was not computed
+
 // Device view of one indexed cloud (all pointers device memory, sorted order).
 struct DevCloud {
-    const double* xyz64;      // [n][4]  x y z 0
+    const PointRec* rec;      // [n]     x y z m0 m1 m2
     const float4* rel32;      // [n]     x y z 0 relative to the tile centre
-    const double4* cov;       // [n]     (a, m0, m1, m2): C = a I - m m^T
+    double eps_a;             // the epsilon the cloud was built with: a of every surface covariance
     const int32_t* perm;      // [n]     sorted -> original index
     const TileInfo* tiles;    // [ntiles]
     const BlockInfo* blocks;  // [nblocks] blocks of 64 tiles, then [ceil(nblocks / 64)] super-blocks of 64 blocks
@@ -112,6 +126,32 @@ struct DevCloud {
     int32_t bits;             // bits per axis (10 for 3-D, 16 for 2-D)
     int32_t dim;
 };
+
+// A record's position alone: one 16-B and one 8-B load, nothing read past z
+struct RecPos {
+    double x, y, z;
+};
+__device__ __forceinline__ RecPos rec_pos(const PointRec* r) {
+    const double2 xy = *reinterpret_cast<const double2*>(r);
+    return RecPos{xy.x, xy.y, r->z};
+}
+// ... and the whole record as its three 16-B words: (x, y), (z, m0), (m1, m2)
+struct RecWords {
+    double2 xy, zm, mm;
+};
+__device__ __forceinline__ RecWords rec_words(const PointRec* r) {
+    const double2* const p = reinterpret_cast<const double2*>(r);
+    return RecWords{p[0], p[1], p[2]};
+}
+
+// (a, m0) of a record's covariance from the words stored (PointRec): the values k_knn_cov computed, bit for bit.
+// m1 and m2 are what the record holds.  A marked row's m1 is +0 (isolated: a = 1, m = 0) or a NaN (not computed:
+// a and m0 take it, so the row reads NaN as the stored words do).
+__device__ __forceinline__ void decode_cov(double eps_a, double m0, double m1, double& a, double& m0d) {
+    const bool marked = m0 != m0;
+    a = marked ? (m1 != m1 ? m1 : 1.0) : eps_a;
+    m0d = marked ? m1 : m0;
+}
 
 // Error bound of the fp32 distance screen: |d2_f32 - d2_f64| <= a sqrt(d2) + b + c d2.
 struct Margin {
@@ -146,7 +186,7 @@ struct CovArgs {
     double eps_a;             // epsilon (a of C = a I - m m^T)
     double m_scale;           // sqrt(epsilon (1 - ratio))
     int32_t min_nb;           // minimum neighbours for a surface covariance
-    double4* cov_out;         // [n] sorted
+    PointRec* rec_out;        // [n] sorted: the cloud's records, whose m this kernel writes
     int32_t* count_out;       // [n] sorted
     int32_t* amb_counter;     // diagnostics (may be null)
     float4* g_nb;             // k_knn_cov<D, K, true>: the graph rows (GraphArgs::nb), [n][kGraphK]
@@ -378,9 +418,9 @@ struct EvalArgs {
     const int64_t* idx;       // [n] matched target row, -1 rejected (CorrArgs::dbg_index)
     const double* dist;       // [n] (CorrArgs::dbg_dist)
     const double* w;          // [n][dim][dim] (CorrArgs::dbg_weight)
-    const double* src_xyz;    // the clouds' sorted fp64 points (DevCloud::xyz64, 4 doubles a row) ...
+    const PointRec* src_xyz;  // the clouds' sorted point records (DevCloud::rec) ...
     const int32_t* src_inv;   // ... and original -> sorted row
-    const double* tgt_xyz;
+    const PointRec* tgt_xyz;
     const int32_t* tgt_inv;
     int64_t n, m;             // source and target rows
     int32_t dim;

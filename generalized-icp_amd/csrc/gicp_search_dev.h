@@ -357,10 +357,9 @@ __device__ __forceinline__ void walk_c(const DevCloud& db, const Query<D>& q, in
 
 __device__ __forceinline__ void stage_f64(const DevCloud& db, const TileInfo& ti, WaveLds& L) {
     const int l = lane_id();
-    double4 v;
+    RecPos v;
     v.x = v.y = v.z = 1e150;
-    v.w = 0.0;
-    if (l < ti.count) v = reinterpret_cast<const double4*>(db.xyz64)[ti.start + l];
+    if (l < ti.count) v = rec_pos(db.rec + (ti.start + l));
     L.t.x64[l] = v.x;
     L.t.y64[l] = v.y;
     L.t.z64[l] = v.z;
@@ -506,7 +505,7 @@ __device__ __forceinline__ int split_query(const DevCloud& cl, int first, int la
     q.valid = l < r1 - r0;
     i = qt.start + r0 + min(l, r1 - r0 - 1);
     const float4 rel = cl.rel32[i];
-    const double4 p4 = reinterpret_cast<const double4*>(cl.xyz64)[i];
+    const RecPos p4 = rec_pos(cl.rec + i);
     const float relv[3] = {rel.x, rel.y, rel.z};
     const double p4v[3] = {p4.x, p4.y, p4.z};
 #pragma unroll

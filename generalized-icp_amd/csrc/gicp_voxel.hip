@@ -210,13 +210,15 @@ __global__ void __launch_bounds__(256) k_voxel_compact(VoxelArgs A, const int32_
     }
 }
 
-// the cloud's points in its original order: out[perm[i]] = xyz64[i]
-__global__ void __launch_bounds__(256) k_points_out(const double* __restrict__ xyz64, const int32_t* __restrict__ perm,
+// the cloud's points in its original order: out[perm[i]] = the position of record i
+__global__ void __launch_bounds__(256) k_points_out(const PointRec* __restrict__ rec, const int32_t* __restrict__ perm,
                                                     int64_t n, int dim, double* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int64_t o = perm[i];
-    for (int a = 0; a < dim; ++a) out[o * dim + a] = xyz64[i * 4 + a];
+    const RecPos p = rec_pos(rec + i);
+    const double pv[3] = {p.x, p.y, p.z};
+    for (int a = 0; a < dim; ++a) out[o * dim + a] = pv[a];
 }
 
 // ---- local voxel map --------------------------------------------------------------------
@@ -419,10 +421,10 @@ hipError_t launch_map_centroids(const double* sums, int64_t m, int dim, int min_
     return hipGetLastError();
 }
 
-hipError_t launch_points_out(const double* xyz64, const int32_t* perm, int64_t n, int dim, double* out, hipStream_t st) {
+hipError_t launch_points_out(const PointRec* rec, const int32_t* perm, int64_t n, int dim, double* out, hipStream_t st) {
     (void)hipGetLastError();
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_points_out, dim3(grid256(n)), dim3(256), 0, st, xyz64, perm, n, dim, out);
+    hipLaunchKernelGGL(k_points_out, dim3(grid256(n)), dim3(256), 0, st, rec, perm, n, dim, out);
     return hipGetLastError();
 }
 

@@ -229,22 +229,24 @@ void begin_build(Cloud& cl, int dim) {
     cl.bits = dim == 3 ? 10 : 16;
 }
 
-// The core of a cloud build: the n points in bs.s_in ([n][dim], device) with bounds mn / mx -> Morton sort,
-// tiles, blocks, covariances and (graph) the neighbour graph.
-void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
-                BuildScratch& bs, const BuildSpec& spec, BuildLog& log) {
+// a build that fails part-way (an unsupported k_neighbors, a HIP error) leaves the cloud NOT SET: cl.n is
+// raised by build_index, before the covariances exist, and every entry point tells a usable cloud by cl.n alone
+struct Unset {
+    Cloud& cl;
+    bool done = false;
+    ~Unset() {
+        if (!done) cl.unset();
+    }
+};
+
+// The index of a cloud alone: the n points in bs.s_in ([n][dim], device) with bounds mn / mx -> Morton sort,
+// tiles, boxes, blocks, rho.  What the searches need of a database or a query set (gicp_knn: no covariances, no
+// graph); build_core goes on from here.
+void build_index(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], BuildScratch& bs,
+                 const BuildSpec& spec, BuildLog& log) {
     hipStream_t st = spec.stream;
-    const bool graph = spec.graph;
     const int tile_points = spec.tile_points;
-    // a build that fails part-way (an unsupported k_neighbors, a HIP error) leaves the cloud NOT SET: cl.n is
-    // raised below, before the covariances exist, and every entry point tells a usable cloud by cl.n alone
-    struct Unset {
-        Cloud& cl;
-        bool done = false;
-        ~Unset() {
-            if (!done) cl.unset();
-        }
-    } unset{cl};
+    for (int a = 0; a < 3; ++a) cl.bb_lo[a] = a < dim ? mn[a] : 0.0, cl.bb_hi[a] = a < dim ? mx[a] : 0.0;
     double ext = 0.0;
     for (int a = 0; a < dim; ++a) ext = std::max(ext, mx[a] - mn[a]);
     ext = ext * (1.0 + 1e-9) + 1e-12 * (1.0 + std::fabs(mn[0]));
@@ -255,8 +257,6 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
     bs.s_codes.reserve((size_t)n);
     bs.s_codes2.reserve((size_t)n);
     bs.s_idx.reserve((size_t)n);
-    if (!bs.d_amb)
-        alloc_init(bs.d_amb, 4, [&](int32_t* d) { HIPCHK(hipMemsetAsync(d, 0, sizeof(int32_t) * 4, st)); });
     double* d_in = bs.s_in;
     uint32_t *d_codes = bs.s_codes, *d_codes_s = bs.s_codes2;
     int32_t *d_idx = bs.s_idx, *d_perm = cl.perm;   // (raw pointers: rocPRIM deduces its iterator types)
@@ -306,6 +306,17 @@ void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const doub
     HIPCHK(hipStreamSynchronize(st));
     std::memcpy(&cl.rho, &rho_bits, sizeof(float));
     log.tick("tiles");
+}
+
+// The core of a cloud build: the index (build_index), then covariances and (graph) the neighbour graph.
+void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
+                BuildScratch& bs, const BuildSpec& spec, BuildLog& log) {
+    hipStream_t st = spec.stream;
+    const bool graph = spec.graph;
+    Unset unset{cl};
+    if (!bs.d_amb)
+        alloc_init(bs.d_amb, 4, [&](int32_t* d) { HIPCHK(hipMemsetAsync(d, 0, sizeof(int32_t) * 4, st)); });
+    build_index(cl, n, dim, mn, mx, bs, spec, log);
 
     // surface covariances (gicp.py:19-35), of this rank's tiles when sharded
     const int qb = 0, qe = shard_tile_count(cl.ntiles, spec.cov_shard, spec.cov_nshards);
@@ -615,6 +626,71 @@ void filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gic
         for (int64_t m = 0; m < fo.M; ++m) out_count[idx[m]] = 0;
     }
     *M_out = fo.M;
+}
+
+// gicp_knn / gicp_knn_points: the k nearest database rows of every query, host out.  The database
+// is the resident cloud, or (resident == nullptr) the M host points xyz, indexed into the context's scratch cloud;
+// the queries are the database's own rows (queries == nullptr) or the Q host points `queries`, indexed in their
+// own frame into a second scratch cloud.  Index-only builds on the context's stream with its synchronous scratch;
+// the tiling's warm-start hint is put back, so a later build of the context's starts as it would have.
+// Everything that can refuse (the finiteness scans) comes before the first write.
+void knn_query(gicp_ctx* c, const Cloud* resident, const double* xyz, int64_t M, const double* queries, int64_t Q, int dim,
+               int k, double max_distance, int64_t* index, double* dist2, int32_t* count) {
+    BuildScratch& bs = c->bs;
+    hipStream_t st = c->stream;
+    double dmn[3], dmx[3], qmn[3], qmx[3];
+    if (!resident) scan_bounds(xyz, M, dim, dmn, dmx);
+    if (queries) scan_bounds(queries, Q, dim, qmn, qmx);
+    auto index_only = [&](Cloud& cl, const double* pts, int64_t n, const double (&mn)[3], const double (&mx)[3]) {
+        const int hint = bs.tile_k_hint[dim & 3];
+        BuildLog log(st);
+        BuildSpec spec;
+        spec.stream = st;
+        begin_build(cl, dim);
+        Unset unset{cl};
+        bs.s_in.reserve((size_t)n * dim);
+        HIPCHK(hipMemcpyAsync(bs.s_in, pts, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
+        build_index(cl, n, dim, mn, mx, bs, spec, log);
+        bs.tile_k_hint[dim & 3] = hint;
+        unset.done = true;
+    };
+    if (!resident) index_only(c->knn_db, xyz, M, dmn, dmx);
+    const Cloud& db = resident ? *resident : c->knn_db;
+    if (queries) index_only(c->knn_q, queries, Q, qmn, qmx);
+    const Cloud& qc = queries ? c->knn_q : db;
+    // d_max of the screen's margin: the diagonal of the union of the two clouds' bounding boxes
+    double diag2 = 0.0;
+    for (int a = 0; a < dim; ++a) {
+        const double e = std::max(db.bb_hi[a], qc.bb_hi[a]) - std::min(db.bb_lo[a], qc.bb_lo[a]);
+        diag2 += e * e;
+    }
+    const int64_t nq = qc.n;
+    c->knn_idx.reserve((size_t)nq * k);
+    c->knn_d2.reserve((size_t)nq * k);
+    c->knn_cnt.reserve((size_t)nq);
+    KnnArgs ka{};
+    ka.qc = qc.view();
+    ka.db = db.view();
+    ka.self = queries ? 0 : 1;
+    ka.k = k;
+    // (under a limit no pair further apart than it matters, as d_n bounds k_knn_cov's)
+    const bool limited = max_distance > 0.0;
+    const double diag = std::sqrt(diag2) * (1.0 + 1e-9);
+    ka.mg = make_margin(dim, qc.rho, db.rho, limited ? std::min(diag, max_distance) : diag);
+    ka.maxd2 = limited ? max_distance * max_distance : INFINITY;
+    ka.search2 = INFINITY;
+    if (limited) {
+        const float s2 = screen_bound(ka.mg, max_distance);
+        if (s2 < 3.0e38f) ka.search2 = s2;   // (a limit beyond the fp32 screen's range limits the exact phase alone)
+    }
+    ka.index = c->knn_idx;
+    ka.dist2 = c->knn_d2;
+    ka.count = c->knn_cnt;
+    HIPCHK(launch_knn_query(ka, st));
+    if (index) HIPCHK(hipMemcpyAsync(index, c->knn_idx, sizeof(int64_t) * nq * k, hipMemcpyDeviceToHost, st));
+    if (dist2) HIPCHK(hipMemcpyAsync(dist2, c->knn_d2, sizeof(double) * nq * k, hipMemcpyDeviceToHost, st));
+    if (count) HIPCHK(hipMemcpyAsync(count, c->knn_cnt, sizeof(int32_t) * nq, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
 }
 
 // gicp_deskew: the sweep xyz with twist xi, de-skewed on the device into `out` (host)

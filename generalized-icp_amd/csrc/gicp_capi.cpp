@@ -82,7 +82,7 @@ void check_sweep_args(const double* xyz, const double* stamps, int64_t N, int di
 
 extern "C" {
 
-int gicp_version(void) { return 105; }
+int gicp_version(void) { return 106; }
 
 int gicp_stats_size(int dim) { return (dim == 2 || dim == 3) ? nstat(dim == 2 ? 2 : 3) : GICP_E_INVALID; }
 
@@ -502,6 +502,32 @@ int gicp_filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const
         check_filter_args(xyz, N, dim, f, out_xyz, M_out);
         *M_out = 0;
         filter_points(c, xyz, N, dim, *f, out_xyz, out_index, out_count, M_out);
+    });
+}
+
+// ---- exact k-nearest-neighbour queries; gicp_knn_host lives in gicp_hostmath.cpp ----
+
+int gicp_knn_max_k(void) { return kKnnMaxK; }
+
+int gicp_knn(gicp_ctx* c, int which, const double* queries, int64_t Q, int dim, int k, double max_distance, int64_t* index,
+             double* dist2, int32_t* count) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_knn", [&] {
+        if (which != 0 && which != 1) throw Fail{GICP_E_INVALID, "which must be 0 (target) or 1 (source)"};
+        check_knn_args(queries, Q, dim, k, max_distance);
+        const Cloud& cl = need_cloud(c, which);
+        if (queries && dim != cl.dim) throw Fail{GICP_E_INVALID, "queries must have the cloud's dim"};
+        knn_query(c, &cl, nullptr, 0, queries, Q, cl.dim, k, max_distance, index, dist2, count);
+    });
+}
+
+int gicp_knn_points(gicp_ctx* c, const double* xyz, int64_t M, const double* queries, int64_t Q, int dim, int k,
+                    double max_distance, int64_t* index, double* dist2, int32_t* count) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_knn_points", [&] {
+        check_cloud_args(xyz, M, dim);
+        check_knn_args(queries, Q, dim, k, max_distance);
+        knn_query(c, nullptr, xyz, M, queries, Q, dim, k, max_distance, index, dist2, count);
     });
 }
 

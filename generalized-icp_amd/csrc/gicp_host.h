@@ -44,6 +44,7 @@ hipError_t launch_map_centroids(const double*, int64_t, int, int, int32_t*, int3
 hipError_t launch_batch_cov(const BatchCovArgs&, int, int, int, hipStream_t);
 hipError_t launch_batch_align(const BatchArgs&, int, int, hipStream_t);
 int batch_max_points(int dim);
+hipError_t launch_knn_query(const KnnArgs&, hipStream_t);
 int corr_grid(int q_tiles, int shard, int nshards);
 int solve_pose(int d, const double* st, const double* Tk, double* Tout, double* loss_out);
 
@@ -71,6 +72,7 @@ struct Cloud {
     double lo[3] = {0, 0, 0};
     double scale = 1.0;
     float rho = 0.f;
+    double bb_lo[3] = {0, 0, 0}, bb_hi[3] = {0, 0, 0};   // exact bounds of the indexed points (the kNN screen's d_max)
     // the epsilon the cloud was built with (a of C = a I - m m^T for every surface point, DevCloud::eps_a): it
     // belongs to the cloud, not to the context's current parameters, and moves with it through every swap
     double eps_a = 0.0;
@@ -374,6 +376,12 @@ struct gicp_ctx {
     gicp::DevBuf<int32_t> b_cnt;
     gicp::DevBuf<gicp::BatchOut> b_out;
     gicp::DevBuf<int64_t> b_dbg_idx;
+    // gicp_knn / gicp_knn_points: the index of an external query set and of a one-shot database
+    // (index only: no covariances, no graph), and the answers before they are copied out; all grow-only
+    gicp::Cloud knn_q, knn_db;
+    gicp::DevBuf<int64_t> knn_idx;
+    gicp::DevBuf<double> knn_d2;
+    gicp::DevBuf<int32_t> knn_cnt;
     static constexpr int kMaxBatch = 64;
     hipEvent_t ev[2 * kMaxBatch] = {};
     int batch_hint = 0;               // iterations the last converging align ran: its first batch next time
@@ -399,6 +407,8 @@ void filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gic
                    int32_t* out_count, int64_t* M_out);
 void deskew_cloud(gicp_ctx* c, const double* xyz, const double* stamps, int64_t N, int dim, const double* xi, double ref,
                   double* out);
+void knn_query(gicp_ctx* c, const Cloud* resident, const double* xyz, int64_t M, const double* queries, int64_t Q, int dim,
+               int k, double max_distance, int64_t* index, double* dist2, int32_t* count);
 void map_insert(gicp_ctx* c, const Cloud* cl, const double* xyz, int64_t n, const double* T);
 void map_to_target(gicp_ctx* c, const gicp_params* p, int min_points);
 void stage_target(gicp_ctx* c, const double* xyz, int64_t M, int dim, const gicp_params* p, int flags, const gicp_sweep* sw);

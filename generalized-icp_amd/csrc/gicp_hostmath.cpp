@@ -569,6 +569,63 @@ void filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter
     else filter_host<2>(xyz, N, *f, out_xyz, out_index, out_count, M_out);
 }
 
+// ---- exact k-nearest-neighbour queries ----
+
+// what gicp_knn, gicp_knn_points and gicp_knn_host refuse alike of the query side (queries == NULL: a self-query,
+// Q and dim are the database's); the finiteness scans are the callers'
+void check_knn_args(const double* queries, int64_t Q, int dim, int k, double max_distance) {
+    if (k < 1 || k > kKnnMaxK) throw Fail{GICP_E_INVALID, "k must be 1..gicp_knn_max_k() (32)"};
+    if (!(std::isfinite(max_distance) && max_distance >= 0.0))
+        throw Fail{GICP_E_INVALID, "max_distance must be finite and >= 0 (0 sets no limit)"};
+    if (!queries) return;
+    if (dim != 2 && dim != 3) throw Fail{GICP_E_INVALID, "dim must be 2 or 3"};
+    if (Q < 1) throw Fail{GICP_E_INVALID, "queries must be a non-empty Q x dim array (Q >= 1)"};
+    if (Q > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "too many queries (> 2^31)"};
+}
+
+namespace {
+// The contract as a loop over all pairs: per query the k first rows of the order (d2, original index).  Rows come
+// in ascending index, so a row displaces a kept one only when its d2 is strictly smaller.
+template <int D>
+void knn_brute(const double* xyz, int64_t M, const double* qs, int64_t Q, int k, double maxd2, int64_t* index, double* dist2,
+               int32_t* count) {
+    std::vector<double> d(k);
+    std::vector<int64_t> id(k);
+    for (int64_t qi = 0; qi < Q; ++qi) {
+        const double* q = qs + qi * D;
+        int n = 0;
+        for (int64_t j = 0; j < M; ++j) {
+            const double d2 = filter_d2<D>(xyz + j * D, q);
+            if (!(d2 <= maxd2) || (n == k && !(d2 < d[k - 1]))) continue;
+            int m = n < k ? n : k - 1;
+            for (; m > 0 && d2 < d[m - 1]; --m) d[m] = d[m - 1], id[m] = id[m - 1];
+            d[m] = d2;
+            id[m] = j;
+            if (n < k) ++n;
+        }
+        for (int m = 0; m < k; ++m) {
+            if (index) index[qi * k + m] = m < n ? id[m] : -1;
+            if (dist2) dist2[qi * k + m] = m < n ? d[m] : INFINITY;
+        }
+        if (count) count[qi] = n;
+    }
+}
+}  // namespace
+
+void knn_host(const double* xyz, int64_t M, const double* queries, int64_t Q, int dim, int k, double max_distance,
+              int64_t* index, double* dist2, int32_t* count) {
+    check_cloud_args(xyz, M, dim);
+    check_knn_args(queries, Q, dim, k, max_distance);
+    double mn[3], mx[3];
+    scan_bounds(xyz, M, dim, mn, mx);   // (the finiteness tests: nothing is written before them)
+    if (queries) scan_bounds(queries, Q, dim, mn, mx);
+    const double* qs = queries ? queries : xyz;
+    const int64_t nq = queries ? Q : M;
+    const double maxd2 = max_distance > 0.0 ? max_distance * max_distance : INFINITY;
+    if (dim == 3) knn_brute<3>(xyz, M, qs, nq, k, maxd2, index, dist2, count);
+    else knn_brute<2>(xyz, M, qs, nq, k, maxd2, index, dist2, count);
+}
+
 // ---- what every entry point checks the same way ----
 
 void check_cloud_args(const double* xyz, int64_t n, int dim) {
@@ -786,6 +843,23 @@ int gicp_filter_points_host(const double* xyz, int64_t N, int dim, const gicp_fi
         const int rc = gicp::current_failure(msg);
         try {
             t_host_err = "gicp_filter_points_host: " + msg;
+        } catch (...) {
+        }
+        return rc == GICP_E_NOMEM ? GICP_E_INVALID : rc;
+    }
+}
+
+// the host yardstick of the k-nearest-neighbour queries: here for the same reason
+int gicp_knn_host(const double* xyz, int64_t M, const double* queries, int64_t Q, int dim, int k, double max_distance,
+                  int64_t* index, double* dist2, int32_t* count) {
+    try {
+        gicp::knn_host(xyz, M, queries, Q, dim, k, max_distance, index, dist2, count);
+        return GICP_OK;
+    } catch (...) {
+        std::string msg;
+        const int rc = gicp::current_failure(msg);
+        try {
+            t_host_err = "gicp_knn_host: " + msg;
         } catch (...) {
         }
         return rc == GICP_E_NOMEM ? GICP_E_INVALID : rc;

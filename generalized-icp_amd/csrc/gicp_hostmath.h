@@ -119,6 +119,11 @@ void check_filter_args(const double* xyz, int64_t N, int dim, const gicp_filter*
 void filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz, int64_t* out_index,
                         int32_t* out_count, int64_t* M_out);
 
+// exact k-nearest-neighbour queries: the argument checks of every entry point, the host yardstick
+void check_knn_args(const double* queries, int64_t Q, int dim, int k, double max_distance);
+void knn_host(const double* xyz, int64_t M, const double* queries, int64_t Q, int dim, int k, double max_distance,
+              int64_t* index, double* dist2, int32_t* count);
+
 // registration report: information matrix of a pass's statistics, symmetric eigensolver
 void information(int dim, const double* stats, const double* T, double* H, double* b);
 void sym_eig(int n, const double* A, double* w, double* V);

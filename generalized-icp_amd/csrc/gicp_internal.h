@@ -475,6 +475,21 @@ struct BatchArgs {
     double* dbg_dist;         // (nullable)
 };
 
+// Exact k-nearest-neighbour queries (gicp_knn.hip): the query cloud qc (indexed in its own frame, or
+// the database itself: a self-query) against the database db.  All pointers device memory.
+constexpr int kKnnMaxK = 32;
+struct KnnArgs {
+    DevCloud qc, db;
+    int32_t self;             // 1: qc is db (a wave's seed tile is its own tile)
+    int32_t k;                // 1 .. K of the instantiation launched
+    float search2;            // fp32 screen bound of max_distance (max_distance^2 + margins); +inf: no limit
+    double maxd2;             // max_distance^2, fp64, inclusive; +inf: no limit
+    Margin mg;
+    int64_t* index;           // [Q][k] original database rows, -1 padded; rows in original query order
+    double* dist2;            // [Q][k] exact d2, +inf padded
+    int32_t* count;           // [Q]
+};
+
 constexpr int nstat(int D) {
     return (D * (D + 1) / 2) * (D * (D + 1) / 2) + (D * (D + 1) / 2) * D + (D * (D + 1) / 2) + D * D + D + 2;
 }

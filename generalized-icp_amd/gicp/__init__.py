@@ -23,7 +23,7 @@ from ._lib import Debug, Params, Report, ReportSpec, Result, Trace, check, dptr
 
 __all__ = ["gicp", "apply_transformation", "Engine", "RotatedCovariances", "expand_stats", "stats_size",
            "default_params", "last_result", "voxel_downsample", "filter_points", "filter_points_host", "deskew", "deskew_host", "motion_twist", "information",
-           "sym_eig", "align_batch", "multistart", "batch_max_points", "pick_start"]
+           "sym_eig", "align_batch", "multistart", "batch_max_points", "pick_start", "knn", "knn_host", "knn_max_k"]
 
 
 def stats_size(dim):
@@ -342,6 +342,35 @@ class Engine:
         check(self._lib.gicp_deskew(self._ctx, dptr(a), dptr(st), a.shape[0], a.shape[1], dptr(M), float(ref),
                                     dptr(out)), self._ctx, "gicp_deskew")
         return out
+
+    def knn(self, queries=None, k=1, max_distance=None, which="target", squared=False):
+        """The k nearest rows of the resident cloud `which` to every query (gicp_knn), exact: fp64
+        d2 = ((dx*dx + dy*dy) + dz*dz), rows ordered by (d2, original index), so exactly equal distances go to the
+        smaller index.  `queries` Q x dim, or None for a self-query (the cloud's own rows, each its own neighbour
+        at distance 0).  max_distance None or 0: no limit, else only rows with d2 <= max_distance**2.  Returns
+        (index [Q, k] int64 padded with -1, distance [Q, k] float64 padded with inf; squared=True: d2 itself).
+        Indices refer to `Engine.points(which)`.  The engine's clouds, caches and settings are untouched."""
+        w = 0 if which == "target" else 1
+        if queries is None:
+            q, nq, dim = None, self.cloud_size(which), 0
+        else:
+            q = _knn_array(queries, "queries")
+            nq, dim = q.shape
+        return _knn_call(lambda *args: check(self._lib.gicp_knn(self._ctx, w, *args), self._ctx, "gicp_knn"),
+                         q, nq, dim, k, max_distance, squared)
+
+    def knn_points(self, points, queries=None, k=1, max_distance=None, squared=False):
+        """gicp.knn on this engine's GPU (gicp_knn_points); the engine's clouds are untouched."""
+        a = _knn_array(points, "points")
+        if queries is None:
+            q, nq = None, a.shape[0]
+        else:
+            q = _knn_array(queries, "queries")
+            nq = q.shape[0]
+            if q.shape[1] != a.shape[1]:
+                raise ValueError(f"queries must be Q x {a.shape[1]} as the points, got shape {q.shape}")
+        return _knn_call(lambda *args: check(self._lib.gicp_knn_points(self._ctx, dptr(a), a.shape[0], *args), self._ctx,
+                                             "gicp_knn_points"), q, nq, a.shape[1], k, max_distance, squared)
 
     def cloud_size(self, which="target"):
         """Points the indexed cloud holds (gicp_cloud_size): the input's length, with set_filter the rows that
@@ -979,6 +1008,59 @@ def filter_points_host(points, center=None, min_range=0.0, max_range=0.0, radius
             raise ValueError(lib.gicp_last_host_error().decode())
 
     return _filter_call(call, a, f, return_index, return_counts)
+
+
+def _knn_array(a, name):
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    if a.ndim != 2:
+        raise ValueError(f"{name} must be a 2-D array of rows, got shape {a.shape}")
+    return a
+
+
+def _knn_call(call, q, nq, dim, k, max_distance, squared):
+    """One kNN entry point: `call` takes (queries, Q, dim, k, max_distance, index, dist2, count) after its own
+    leading arguments and raises if the library refuses; the outputs are allocated once the sizes are plausible."""
+    k = int(k)
+    rows = max(int(nq), 1) if 1 <= k <= knn_max_k() else 1
+    idx = np.empty((rows, max(k, 1)), dtype=np.int64)
+    d2 = np.empty((rows, max(k, 1)))
+    call(dptr(q) if q is not None else None, int(nq), int(dim), k, 0.0 if max_distance is None else float(max_distance),
+         idx.ctypes.data_as(C.POINTER(C.c_int64)), dptr(d2), None)
+    return idx, (d2 if squared else np.sqrt(d2))
+
+
+def knn_max_k():
+    """The largest k of `knn` (gicp_knn_max_k)."""
+    return int(_lib.load().gicp_knn_max_k())
+
+
+def knn(points, queries=None, k=1, max_distance=None, squared=False, device=0):
+    """Exact k nearest neighbours on the GPU (gicp_knn_points, DESIGN.md §3r): for every row of `queries` (Q x dim;
+    None: the rows of `points` themselves) the k rows of `points` (M x 2 or M x 3) nearest to it.  The distance is
+    the fp64 expression d2 = ((dx*dx + dy*dy) + dz*dz), every operation rounded on its own; rows are ordered by
+    (d2, row), so exactly equal distances go to the smaller row -- the library's own rule, not a KD-tree's.
+    max_distance None or 0: no limit, else only rows with d2 <= max_distance**2 count.  Returns (index [Q, k] int64
+    padded with -1, distance [Q, k] float64 padded with inf); squared=True returns d2 itself.  Deterministic.
+    Raises ValueError for k outside 1..knn_max_k(), non-finite input, an empty array and a negative or non-finite
+    max_distance."""
+    return _engine(int(device)).knn_points(points, queries, k, max_distance, squared)
+
+
+def knn_host(points, queries=None, k=1, max_distance=None):
+    """`knn` computed on the host by a brute force over all pairs (gicp_knn_host; no GPU needed): the CPU
+    yardstick.  Returns (index, d2): always the squared distances."""
+    a = _knn_array(points, "points")
+    q = None if queries is None else _knn_array(queries, "queries")
+    if q is not None and q.shape[1] != a.shape[1]:
+        raise ValueError(f"queries must be Q x {a.shape[1]} as the points, got shape {q.shape}")
+    lib = _lib.load()
+
+    def call(*args):
+        rc = lib.gicp_knn_host(dptr(a), a.shape[0], *args)
+        if rc != _lib.GICP_OK:   # (host only: the message is the thread's, there is no context)
+            raise ValueError(lib.gicp_last_host_error().decode())
+
+    return _knn_call(call, q, a.shape[0] if q is None else q.shape[0], a.shape[1], k, max_distance, True)
 
 
 def deskew(points, stamps, motion, ref=0.0, device=0):

@@ -275,6 +275,13 @@ SIGNATURES = {
     "gicp_batch_max_points": (C.c_int, [C.c_int]),
     "gicp_batch_align": (C.c_int, [_VP, C.c_int, _DP, C.POINTER(C.c_int64), C.c_int, C.POINTER(BatchProblem), C.c_int,
                                    C.POINTER(Params), _DP, C.POINTER(BatchResult), C.POINTER(BatchDebug)]),
+    "gicp_knn_max_k": (C.c_int, []),
+    "gicp_knn": (C.c_int, [_VP, C.c_int, _DP, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), _DP,
+                           C.POINTER(C.c_int32)]),
+    "gicp_knn_points": (C.c_int, [_VP, _DP, C.c_int64, _DP, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64),
+                                  _DP, C.POINTER(C.c_int32)]),
+    "gicp_knn_host": (C.c_int, [_DP, C.c_int64, _DP, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), _DP,
+                                C.POINTER(C.c_int32)]),
 }
 
 # gicp_allreduce_fn: int (*)(double* buf, int n, void* user)
@@ -287,6 +294,7 @@ HASH_SRCS = ("csrc/gicp_index.hip", "csrc/gicp_cov.hip", "csrc/gicp_corr.hip", "
              "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
              "csrc/gicp_build.cpp", "csrc/gicp_align.cpp", "csrc/gicp_exchange.cpp", "csrc/gicp_voxel.hip",
              "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_filter.hip", "csrc/gicp_batch.hip", "csrc/gicp_batch.cpp",
+             "csrc/gicp_knn.hip",
              "csrc/gicp_internal.h", "csrc/gicp_mem.h",
              "csrc/gicp_sweep.h", "csrc/gicp_filter.h", "csrc/gicp_cov_dev.h", "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
              "../include/gicp_hip.h",

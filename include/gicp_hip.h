@@ -161,7 +161,9 @@ int gicp_version(void);                          /* 100 * major + minor; 101: gi
                                                     registration report (gicp_evaluate, gicp_information,
                                                     gicp_sym_eig); 104: the input filters (gicp_filter,
                                                     gicp_filter_points[_host], gicp_set_filter); 105: batched
-                                                    registration (gicp_batch_align, gicp_batch_max_points) */
+                                                    registration (gicp_batch_align, gicp_batch_max_points); 106:
+                                                    exact k-nearest-neighbour queries (gicp_knn, gicp_knn_points,
+                                                    gicp_knn_host, gicp_knn_max_k) */
 int gicp_stats_size(int dim);                    /* 26 (dim 2) or 74 (dim 3) */
 void gicp_default_params(int dim, gicp_params* out);
 const char* gicp_strerror(int code);
@@ -495,7 +497,7 @@ int gicp_filter_points(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, con
                        int64_t* out_index, int32_t* out_count, int64_t* M_out);
 int gicp_filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz,
                             int64_t* out_index, int32_t* out_count, int64_t* M_out);
-const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host or refused gicp_batch_align ("" if none) */
+const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host or gicp_knn_host, or refused gicp_batch_align ("" if none) */
 int gicp_set_filter(gicp_ctx* ctx, const gicp_filter* f);
 
 /* ---- local voxel map ----------------------------------------------------------------
@@ -668,6 +670,41 @@ int gicp_batch_align(gicp_ctx* ctx, int dim, const double* xyz, const int64_t* o
                      const gicp_batch_problem* problems, int n_problems, const gicp_params* p,
                      double* T_out /* [n_problems][(dim+1)^2] */, gicp_batch_result* res /* [n_problems], may be NULL */,
                      gicp_batch_debug* dbg /* may be NULL */);
+
+/* ---- exact k-nearest-neighbour queries ------------------------------------------------
+ * The k nearest rows of a database cloud P (M rows) to each query point q, from the index the engine builds for
+ * every cloud, 1 <= k <= gicp_knn_max_k().
+ *   DISTANCE  d2(q, p) = ((dx * dx + dy * dy) + dz * dz) in fp64, dx = p_x - q_x, every product and every sum
+ *             rounded on its own (no FMA), the z term dropped in 2-D: the bits NumPy's expression gives.
+ *   ORDER     rows are ordered by (d2, original index), ascending: exactly equal distances go to the SMALLER
+ *             original index.  The result is the first k rows of that order.  (The library's own rule; a KD-tree's
+ *             choice at exact ties follows its traversal.)
+ *   LIMIT     max_distance must be finite and >= 0; 0 sets no limit, otherwise only rows with
+ *             d2 <= max_distance * max_distance (the product rounded once, the bound inclusive) are kept.
+ *   OUTPUT    per query, in the caller's query order: index[k] the original rows (int64, padded with -1), dist2[k]
+ *             their exact d2 (fp64, padded with +inf), count the number of real entries (int32).  Any of the three
+ *             may be NULL.  The same inputs give the same bits on every call, context and GPU.
+ * gicp_knn asks the resident cloud `which` (0 target, 1 source): its rows and indices are those of
+ * gicp_get_points (the filtered cloud under gicp_set_voxel / gicp_set_filter; source shards do not matter).
+ * queries == NULL is a SELF-QUERY: the queries are the cloud's own rows in original order (Q and dim are ignored),
+ * so a row is its own neighbour at d2 = 0 and, among coincident rows, the lowest index comes first.  Nothing of the
+ * context is used or changed beyond that cloud's index: not its staged targets, pose-dependent caches or filter
+ * settings; an align gives the same bits with or without such calls around it.
+ * gicp_knn_points is the one-shot: it indexes xyz (no covariances, no graph) into scratch and answers; the
+ * context's clouds are untouched.  gicp_knn_host is host only (no HIP call, no context): a brute force over all
+ * pairs, the CPU yardstick; its message is gicp_last_host_error()'s.
+ * GICP_E_INVALID for: k outside 1 .. gicp_knn_max_k(); a dim other than 2 or 3, or other than the cloud's; Q < 1 or
+ * M < 1; a non-finite query or point; a max_distance that is negative or not finite.  GICP_E_STATE when the
+ * resident cloud is not set.  A refused call writes nothing.  The call is synchronous on the context's stream (one
+ * stream synchronisation for a self-query of a resident cloud; indexing a query set or a one-shot database adds
+ * the two of an index build each); scratch is grow-only. */
+int gicp_knn_max_k(void);   /* 32 */
+int gicp_knn(gicp_ctx* ctx, int which, const double* queries, int64_t Q, int dim, int k, double max_distance,
+             int64_t* index /* [Q][k] */, double* dist2 /* [Q][k] */, int32_t* count /* [Q] */);
+int gicp_knn_points(gicp_ctx* ctx, const double* xyz, int64_t M, const double* queries, int64_t Q, int dim, int k,
+                    double max_distance, int64_t* index, double* dist2, int32_t* count);
+int gicp_knn_host(const double* xyz, int64_t M, const double* queries, int64_t Q, int dim, int k, double max_distance,
+                  int64_t* index, double* dist2, int32_t* count);
 
 #ifdef __cplusplus
 }

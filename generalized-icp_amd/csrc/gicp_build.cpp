@@ -239,11 +239,11 @@ struct Unset {
     }
 };
 
-// The index of a cloud alone: the n points in bs.s_in ([n][dim], device) with bounds mn / mx -> Morton sort,
-// tiles, boxes, blocks, rho.  What the searches need of a database or a query set (gicp_knn: no covariances, no
-// graph); build_core goes on from here.
+// The index of a cloud alone: the n points in bs.s_in ([n][dim], device; or in `pts` when given) with bounds
+// mn / mx -> Morton sort, tiles, boxes, blocks, rho.  What the searches need of a database or a query set (gicp_knn:
+// no covariances, no graph); build_core goes on from here.
 void build_index(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], BuildScratch& bs,
-                 const BuildSpec& spec, BuildLog& log) {
+                 const BuildSpec& spec, BuildLog& log, const double* pts = nullptr) {
     hipStream_t st = spec.stream;
     const int tile_points = spec.tile_points;
     for (int a = 0; a < 3; ++a) cl.bb_lo[a] = a < dim ? mn[a] : 0.0, cl.bb_hi[a] = a < dim ? mx[a] : 0.0;
@@ -257,7 +257,7 @@ void build_index(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const dou
     bs.s_codes.reserve((size_t)n);
     bs.s_codes2.reserve((size_t)n);
     bs.s_idx.reserve((size_t)n);
-    double* d_in = bs.s_in;
+    const double* d_in = pts ? pts : bs.s_in.get();
     uint32_t *d_codes = bs.s_codes, *d_codes_s = bs.s_codes2;
     int32_t *d_idx = bs.s_idx, *d_perm = cl.perm;   // (raw pointers: rocPRIM deduces its iterator types)
     DevCloud fr = cl.view();
@@ -306,6 +306,99 @@ void build_index(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const dou
     HIPCHK(hipStreamSynchronize(st));
     std::memcpy(&cl.rho, &rho_bits, sizeof(float));
     log.tick("tiles");
+}
+
+// Statistical outlier removal (gicp_sor.hip) of the device cloud d_in [m][dim] with bounds mn / mx:
+// an index-only build of the rows into the scratch's own cloud, the self-query for k + 1 neighbours, the means, the
+// two tree sums, the flags, the compaction into d_out (never d_in).  track: also the input row of each
+// survivor; stats [3] (nullable): mu, sigma, thr.  The means stay
+// in bs.o_mean.  One stream sync beyond the index build's two; the result words and doubles are all that returns.
+// The tiling's warm-start hint is put back, so the build that follows starts as it would have.
+FilterOut sor_stage(BuildScratch& bs, const double* d_in, int64_t m, int dim, const double (&mn)[3], const double (&mx)[3],
+                    const gicp_sor& s, double* d_out, bool track, double* stats, BuildLog& log,
+                    hipStream_t st) {
+    check_sor_rows(m);
+    check_sor_extent(dim, mn, mx);
+    Cloud& cl = bs.o_cl;
+    {
+        const int hint = bs.tile_k_hint[dim & 3];
+        BuildLog ilog(st);   // (the index's own phases are not the build's)
+        ilog.verbose = false;
+        BuildSpec spec;
+        spec.stream = st;
+        begin_build(cl, dim);
+        Unset unset{cl};
+        build_index(cl, m, dim, mn, mx, bs, spec, ilog, d_in);
+        bs.tile_k_hint[dim & 3] = hint;
+        unset.done = true;
+    }
+    log.tick("sor-index");
+    const int kk = s.k + 1;
+    bs.o_idx.reserve((size_t)m * kk);
+    bs.o_d2.reserve((size_t)m * kk);
+    bs.o_cnt.reserve((size_t)m);
+    KnnArgs ka{};
+    ka.qc = cl.view();
+    ka.db = ka.qc;
+    ka.self = 1;
+    ka.k = kk;
+    double diag2 = 0.0;   // d_max of the screen's margin: the diagonal of the bounding box
+    for (int a = 0; a < dim; ++a) {
+        const double e = cl.bb_hi[a] - cl.bb_lo[a];
+        diag2 += e * e;
+    }
+    ka.mg = make_margin(dim, cl.rho, cl.rho, std::sqrt(diag2) * (1.0 + 1e-9));
+    ka.maxd2 = INFINITY;
+    ka.search2 = INFINITY;
+    ka.index = bs.o_idx;
+    ka.dist2 = bs.o_d2;
+    ka.count = bs.o_cnt;
+    HIPCHK(launch_knn_query(ka, st));
+    log.tick("sor-query");
+    bs.o_mean.reserve((size_t)m);
+    bs.o_part.reserve(sor_part_count(m));
+    bs.o_stats.reserve((size_t)kSorStats + 2);
+    bs.f_keep.reserve((size_t)m);
+    bs.f_pos.reserve((size_t)m);
+    if (track) bs.o_rows.reserve((size_t)m);
+    if (!bs.v_res) bs.v_res.alloc((size_t)kVoxelRes);
+    size_t tmp_bytes = 0;
+    HIPCHK(voxel_temp_bytes(m, 1, &tmp_bytes, st));
+    bs.v_tmp.reserve(tmp_bytes + 16);
+    SorArgs sa{};
+    sa.in = d_in;
+    sa.n = m;
+    sa.dim = dim;
+    sa.k = s.k;
+    sa.std_ratio = s.std_ratio;
+    sa.d2 = bs.o_d2;
+    sa.cnt = bs.o_cnt;
+    sa.mean = bs.o_mean;
+    sa.part = bs.o_part;
+    sa.stats = bs.o_stats;
+    sa.sums = bs.o_stats.get() + kSorStats;
+    sa.keep = bs.f_keep;
+    sa.pos1 = bs.f_pos;
+    sa.tmp = bs.v_tmp;
+    sa.tmp_bytes = tmp_bytes;
+    sa.out = d_out;
+    sa.idx_out = track ? bs.o_rows.get() : nullptr;
+    sa.res = bs.v_res;
+    HIPCHK(launch_sor(sa, st));
+    double hs[kSorStats];
+    unsigned long long res[kVoxelRes];
+    HIPCHK(hipMemcpyAsync(hs, bs.o_stats, sizeof hs, hipMemcpyDeviceToHost, st));
+    read_result_words(bs, res, st);
+    FilterOut fo;
+    fo.M = (int64_t)res[6];
+    log.tick("sor-reduce");
+    check_sor_result(hs[0], fo.M, m, s);
+    decode_bounds(res, dim, fo.mn, fo.mx);
+    fo.pts = d_out;
+    fo.idx = sa.idx_out;
+    if (stats)
+        for (int a = 0; a < 3; ++a) stats[a] = hs[1 + a];
+    return fo;
 }
 
 // The core of a cloud build: the index (build_index), then covariances and (graph) the neighbour graph.
@@ -487,19 +580,26 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
         log.tick("deskew");
     };
     // (a staged build passes its pinned copy: the H2D copy is then asynchronous)
-    if (filter_on(spec.filter)) {
-        // upload, de-skew, crop, radius outlier removal, voxel filter, index: every stage hands the next one its
-        // survivors and their exact bounds on the device; the last input filter writes where the index reads
+    const bool sor = spec.sor.k > 0;
+    if (filter_on(spec.filter) || sor) {
+        // upload, de-skew, crop, radius outlier removal, statistical outlier removal, voxel filter, index: every
+        // stage hands the next one its survivors and their exact bounds on the device; the last input filter writes
+        // where the index reads
         const bool voxel = spec.voxel_leaf > 0.0;
         bs.v_raw.reserve((size_t)n * dim);
         HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
         log.tick("upload");
         if (spec.sweep) deskew(bs.v_raw);
-        const FilterOut fo = filter_stages(bs, bs.v_raw, n, dim, mn, mx, spec.filter, voxel ? nullptr : bs.s_in.get(), false,
-                                           nullptr, st);
+        FilterOut fo = filter_stages(bs, bs.v_raw, n, dim, mn, mx, spec.filter, voxel || sor ? nullptr : bs.s_in.get(), false,
+                                     nullptr, st);
+        log.tick("filter");
+        if (sor) {
+            if (voxel) bs.o_pts.reserve((size_t)fo.M * dim);
+            fo = sor_stage(bs, fo.pts, fo.M, dim, fo.mn, fo.mx, spec.sor, voxel ? bs.o_pts.get() : bs.s_in.get(), false, nullptr,
+                           log, st);
+        }
         n = fo.M;
         for (int a = 0; a < 3; ++a) mn[a] = fo.mn[a], mx[a] = fo.mx[a];
-        log.tick("filter");
         if (voxel) {
             const VoxelOut vo = voxel_filter(bs, fo.pts, n, dim, mn, mx, spec.voxel_leaf, spec.voxel_min, bs.s_in, st);
             n = vo.M;
@@ -528,6 +628,7 @@ BuildSpec target_spec(const gicp_ctx* c, hipStream_t st) {
     spec.voxel_leaf = c->voxel_leaf;
     spec.voxel_min = c->voxel_min;
     spec.filter = c->filt;
+    spec.sor = c->sor;
     spec.stream = st;
     return spec;
 }
@@ -541,6 +642,7 @@ BuildSpec source_spec(const gicp_ctx* c, int shard, int nshards) {
     spec.voxel_leaf = c->voxel_leaf;
     spec.voxel_min = c->voxel_min;
     spec.filter = c->filt;
+    spec.sor = c->sor;
     spec.stream = c->stream;
     return spec;
 }
@@ -625,6 +727,30 @@ void filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gic
         for (int64_t i = 0; i < N; ++i) out_count[i] = -1;
         for (int64_t m = 0; m < fo.M; ++m) out_count[idx[m]] = 0;
     }
+    *M_out = fo.M;
+}
+
+// gicp_sor_points: the one-shot of statistical outlier removal, host in, host out; every output may be null
+void sor_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_sor& s,
+                double* out_xyz, int64_t* out_index, double* out_mean, double* out_stats, int64_t* M_out) {
+    BuildScratch& bs = c->bs;
+    hipStream_t st = c->stream;
+    bs.v_raw.reserve((size_t)N * dim);
+    bs.o_pts.reserve((size_t)N * dim);
+    HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * N * dim, hipMemcpyHostToDevice, st));
+    double stats[3];
+    BuildLog log(st);
+    log.verbose = false;   // (nothing prints a one-shot's phases: no synchronisation for them)
+    const FilterOut fo = sor_stage(bs, bs.v_raw, N, dim, mn, mx, s, bs.o_pts, out_index != nullptr, stats, log, st);
+    std::vector<int32_t> idx(out_index ? (size_t)fo.M : 0);
+    if (out_xyz) HIPCHK(hipMemcpyAsync(out_xyz, fo.pts, sizeof(double) * fo.M * dim, hipMemcpyDeviceToHost, st));
+    if (out_index) HIPCHK(hipMemcpyAsync(idx.data(), fo.idx, sizeof(int32_t) * fo.M, hipMemcpyDeviceToHost, st));
+    if (out_mean) HIPCHK(hipMemcpyAsync(out_mean, bs.o_mean, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (out_index)
+        for (int64_t m = 0; m < fo.M; ++m) out_index[m] = idx[m];
+    if (out_stats)
+        for (int a = 0; a < 3; ++a) out_stats[a] = stats[a];
     *M_out = fo.M;
 }
 

@@ -82,7 +82,7 @@ void check_sweep_args(const double* xyz, const double* stamps, int64_t N, int di
 
 extern "C" {
 
-int gicp_version(void) { return 106; }
+int gicp_version(void) { return 107; }
 
 int gicp_stats_size(int dim) { return (dim == 2 || dim == 3) ? nstat(dim == 2 ? 2 : 3) : GICP_E_INVALID; }
 
@@ -528,6 +528,33 @@ int gicp_knn_points(gicp_ctx* c, const double* xyz, int64_t M, const double* que
         check_cloud_args(xyz, M, dim);
         check_knn_args(queries, Q, dim, k, max_distance);
         knn_query(c, nullptr, xyz, M, queries, Q, dim, k, max_distance, index, dist2, count);
+    });
+}
+
+// ---- statistical outlier removal; gicp_sor_points_host lives in gicp_hostmath.cpp ----
+
+int gicp_sor_max_k(void) { return kSorMaxK; }
+
+int gicp_set_sor(gicp_ctx* c, const gicp_sor* s) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_set_sor", [&] {
+        gicp_sor v{};
+        if (s && s->k != 0) {
+            check_sor(*s);
+            v = *s;
+            v.pad = 0;
+        }
+        c->sor = v;
+    });
+}
+
+int gicp_sor_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gicp_sor* s, double* out_xyz, int64_t* out_index,
+                    double* out_mean, double* out_stats, int64_t* M_out) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_sor_points", [&] {
+        double mn[3], mx[3];
+        check_sor_args(xyz, N, dim, s, M_out, mn, mx);   // (the one scan of the cloud: finiteness and bounds)
+        sor_points(c, xyz, N, dim, mn, mx, *s, out_xyz, out_index, out_mean, out_stats, M_out);
     });
 }
 

@@ -202,4 +202,14 @@ hipError_t launch_ror(const VoxelArgs& V, const RorArgs& R, hipStream_t st) {
     return V.dim == 3 ? ror<3>(V, R, st) : ror<2>(V, R, st);
 }
 
+// The stages' last step for a filter of another file (gicp_sor.hip): keep flags -> scan -> k_filter_compact.  The
+// result words hold min = all ones, max = 0, M = 0 when this runs.
+hipError_t launch_filter_compact(const double* in, int64_t n, int dim, int32_t* keep, int32_t* pos1, void* tmp,
+                                 size_t tmp_bytes, const int32_t* idx_in, double* out, int32_t* idx_out,
+                                 unsigned long long* res, hipStream_t st) {
+    if (n <= 0 || (dim != 2 && dim != 3) || !in || !out || !keep || !pos1 || !res) return hipErrorInvalidValue;
+    return dim == 3 ? compact<3>(in, n, keep, pos1, tmp, tmp_bytes, idx_in, out, idx_out, res, st)
+                    : compact<2>(in, n, keep, pos1, tmp, tmp_bytes, idx_in, out, idx_out, res, st);
+}
+
 }  // namespace gicp

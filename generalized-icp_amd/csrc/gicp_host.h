@@ -15,6 +15,7 @@
 
 #include "gicp_filter.h"
 #include "gicp_hostmath.h"
+#include "gicp_sor.h"
 #include "gicp_sweep.h"
 
 namespace gicp {
@@ -45,6 +46,8 @@ hipError_t launch_batch_cov(const BatchCovArgs&, int, int, int, hipStream_t);
 hipError_t launch_batch_align(const BatchArgs&, int, int, hipStream_t);
 int batch_max_points(int dim);
 hipError_t launch_knn_query(const KnnArgs&, hipStream_t);
+hipError_t launch_sor(const SorArgs&, hipStream_t);
+size_t sor_part_count(int64_t n);
 int corr_grid(int q_tiles, int shard, int nshards);
 int solve_pose(int d, const double* st, const double* Tk, double* Tout, double* loss_out);
 
@@ -166,6 +169,12 @@ struct BuildScratch {
     // keys, the sort's scratch and the result words are the voxel filter's
     DevBuf<double> f_pts[2], f_packed;
     DevBuf<int32_t> f_keep, f_pos, f_idx[2], f_cnt;
+    // statistical outlier removal (gicp_sor.hip): the index of the stage's rows (index only) and the
+    // self-query's answers, the means, the trees' partials, the sums and result doubles, the survivors and their rows
+    Cloud o_cl;
+    DevBuf<int64_t> o_idx;
+    DevBuf<double> o_d2, o_mean, o_part, o_stats, o_pts;
+    DevBuf<int32_t> o_cnt, o_rows;
     std::unique_ptr<WorkerPool> pool;  // tiling threads (lazily started)
     WorkerPool& workers() {
         if (!pool) {
@@ -206,6 +215,8 @@ struct BuildSpec {
     int voxel_min = 1;
     // the input filters, run after the de-skew and before the voxel filter; all-zero: off
     gicp_filter filter{};
+    // statistical outlier removal, run after the input filters and before the voxel filter; k = 0: off
+    gicp_sor sor{};
     // sweep: the uploaded cloud is first de-skewed on the device, point i moved by
     // Exp((stamps[i] - ref) Log(motion)); the filter and the index then see the de-skewed points and their bounds.
     // The twist is taken from `motion` ((dim+1)^2 row-major) once the build has begun, so a motion it refuses
@@ -291,6 +302,7 @@ struct gicp_ctx {
     double voxel_leaf = 0.0;
     int voxel_min = 1;
     gicp_filter filt{};               // input filters of every later cloud build (gicp_set_filter): all-zero = off
+    gicp_sor sor{};                   // statistical outlier removal of every later cloud build (gicp_set_sor): k = 0 = off
     gicp::VoxelMap map;               // local voxel map (gicp_map_reset)
     // staged targets (gicp_stage_target / gicp_commit_target): a ring of GICP_MAX_STAGED slots, each
     // built into its own cloud on its own stream by a host thread while the current target is
@@ -405,6 +417,8 @@ void voxel_downsample(gicp_ctx* c, const double* xyz, int64_t N, int dim, double
                       int32_t* out_count, int64_t* M_out);
 void filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gicp_filter& f, double* out_xyz, int64_t* out_index,
                    int32_t* out_count, int64_t* M_out);
+void sor_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_sor& s,
+                double* out_xyz, int64_t* out_index, double* out_mean, double* out_stats, int64_t* M_out);
 void deskew_cloud(gicp_ctx* c, const double* xyz, const double* stamps, int64_t N, int dim, const double* xi, double ref,
                   double* out);
 void knn_query(gicp_ctx* c, const Cloud* resident, const double* xyz, int64_t M, const double* queries, int64_t Q, int dim,

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "gicp_filter.h"
+#include "gicp_sor.h"
 #include "gicp_sweep.h"
 
 namespace gicp {
@@ -626,6 +627,114 @@ void knn_host(const double* xyz, int64_t M, const double* queries, int64_t Q, in
     else knn_brute<2>(xyz, M, qs, nq, k, maxd2, index, dist2, count);
 }
 
+// ---- statistical outlier removal (gicp_sor.h) ----
+
+// what gicp_set_sor, gicp_sor_points and gicp_sor_points_host refuse alike of the setting
+void check_sor(const gicp_sor& s) {
+    if (s.k < 1 || s.k > kSorMaxK) throw Fail{GICP_E_INVALID, "sor: k must be 1..gicp_sor_max_k() (31)"};
+    if (!(std::isfinite(s.std_ratio) && s.std_ratio >= 0.0)) throw Fail{GICP_E_INVALID, "sor: std_ratio must be finite and >= 0"};
+}
+
+// a stage needs two rows: a row's neighbours are the others
+void check_sor_rows(int64_t m) {
+    if (m >= 2) return;
+    char b[128];
+    std::snprintf(b, sizeof b, "sor: statistical outlier removal needs at least 2 rows (the stage got %lld)", (long long)m);
+    throw Fail{GICP_E_INVALID, b};
+}
+
+// A stage's rows must span a squared extent that fp64 holds: beyond it d2 between rows overflows, the sum of the
+// means need not be finite, and the search's margin (the diagonal) is infinite.  Refused before anything is launched,
+// by the device path and the host yardstick alike.
+void check_sor_extent(int dim, const double (&mn)[3], const double (&mx)[3]) {
+    double diag2 = 0.0;
+    for (int a = 0; a < dim; ++a) {
+        const double e = mx[a] - mn[a];
+        diag2 += e * e;
+    }
+    if (!std::isfinite(diag2)) throw Fail{GICP_E_INVALID, "sor: the squared extent of the rows is not finite (the cloud is too wide for fp64 distances)"};
+}
+
+// the argument checks of both one-shot entry points, the finiteness test and the bounds it yields
+void check_sor_args(const double* xyz, int64_t N, int dim, const gicp_sor* s, const int64_t* M_out, double (&mn)[3],
+                    double (&mx)[3]) {
+    check_cloud_args(xyz, N, dim);
+    if (!s) throw Fail{GICP_E_INVALID, "sor must not be NULL"};
+    if (!M_out) throw Fail{GICP_E_INVALID, "M_out must not be NULL"};
+    check_sor(*s);
+    check_sor_rows(N);
+    scan_bounds(xyz, N, dim, mn, mx);
+    check_sor_extent(dim, mn, mx);
+}
+
+// what a stage of m rows refuses of its own result: a sum of the means that is not finite, no row kept
+void check_sor_result(double t_mean, int64_t kept, int64_t m, const gicp_sor& s) {
+    char b[200];
+    if (!std::isfinite(t_mean)) {
+        std::snprintf(b, sizeof b, "sor: the sum of the %lld mean neighbour distances is not finite (the cloud is too wide for fp64)",
+                      (long long)m);
+        throw Fail{GICP_E_INVALID, b};
+    }
+    if (kept <= 0) {
+        std::snprintf(b, sizeof b, "sor: statistical outlier removal removed all %lld points (k %d, std_ratio %g)", (long long)m,
+                      (int)s.k, s.std_ratio);
+        throw Fail{GICP_E_INVALID, b};
+    }
+}
+
+namespace {
+// T(v): the pairwise tree in row order (an odd element is carried: it would meet the +0.0 of the padding)
+double sor_tree(std::vector<double>& v) {
+    size_t n = v.size();
+    while (n > 1) {
+        const size_t h = n / 2;
+        for (size_t i = 0; i < h; ++i) v[i] = sor_add(v[2 * i], v[2 * i + 1]);
+        if (n & 1) v[h] = sor_add(v[n - 1], 0.0);
+        n = h + (n & 1);
+    }
+    return v[0];
+}
+
+template <int D>
+void sor_host(const double* xyz, int64_t N, const gicp_sor& s, double* out_xyz, int64_t* out_index, double* out_mean,
+              double* out_stats, int64_t* M_out) {
+    // the self-query for k + 1 rows; entry 0 is the row's own zero, or that of a coincident row of lower index
+    const int kk = s.k + 1;
+    std::vector<double> d2((size_t)N * kk);
+    std::vector<int32_t> cnt((size_t)N);
+    knn_brute<D>(xyz, N, xyz, N, kk, INFINITY, nullptr, d2.data(), cnt.data());
+    std::vector<double> mean((size_t)N), v((size_t)N);
+    for (int64_t i = 0; i < N; ++i) v[i] = mean[i] = sor_mean(&d2[(size_t)i * kk + 1], cnt[i] - 1);
+    const double t = sor_tree(v);
+    const double mu = sor_mu(t, N);
+    for (int64_t i = 0; i < N; ++i) v[i] = sor_dev2(mean[i], mu);
+    const double sigma = sor_sigma(sor_tree(v), N);
+    const double thr = sor_thr(mu, s.std_ratio, sigma);
+    int64_t M = 0;
+    for (int64_t i = 0; i < N; ++i) M += sor_keeps(mean[i], thr) ? 1 : 0;
+    check_sor_result(t, M, N, s);
+    M = 0;
+    for (int64_t i = 0; i < N; ++i) {
+        if (out_mean) out_mean[i] = mean[i];
+        if (!sor_keeps(mean[i], thr)) continue;
+        if (out_xyz)
+            for (int a = 0; a < D; ++a) out_xyz[M * D + a] = xyz[i * D + a];
+        if (out_index) out_index[M] = i;
+        ++M;
+    }
+    if (out_stats) out_stats[0] = mu, out_stats[1] = sigma, out_stats[2] = thr;
+    *M_out = M;
+}
+}  // namespace
+
+void sor_points_host(const double* xyz, int64_t N, int dim, const gicp_sor* s, double* out_xyz, int64_t* out_index,
+                     double* out_mean, double* out_stats, int64_t* M_out) {
+    double mn[3], mx[3];
+    check_sor_args(xyz, N, dim, s, M_out, mn, mx);   // (a refused call writes nothing, *M_out included)
+    if (dim == 3) sor_host<3>(xyz, N, *s, out_xyz, out_index, out_mean, out_stats, M_out);
+    else sor_host<2>(xyz, N, *s, out_xyz, out_index, out_mean, out_stats, M_out);
+}
+
 // ---- what every entry point checks the same way ----
 
 void check_cloud_args(const double* xyz, int64_t n, int dim) {
@@ -860,6 +969,23 @@ int gicp_knn_host(const double* xyz, int64_t M, const double* queries, int64_t Q
         const int rc = gicp::current_failure(msg);
         try {
             t_host_err = "gicp_knn_host: " + msg;
+        } catch (...) {
+        }
+        return rc == GICP_E_NOMEM ? GICP_E_INVALID : rc;
+    }
+}
+
+// ... and of statistical outlier removal
+int gicp_sor_points_host(const double* xyz, int64_t N, int dim, const gicp_sor* s, double* out_xyz, int64_t* out_index,
+                         double* out_mean, double* out_stats, int64_t* M_out) {
+    try {
+        gicp::sor_points_host(xyz, N, dim, s, out_xyz, out_index, out_mean, out_stats, M_out);
+        return GICP_OK;
+    } catch (...) {
+        std::string msg;
+        const int rc = gicp::current_failure(msg);
+        try {
+            t_host_err = "gicp_sor_points_host: " + msg;
         } catch (...) {
         }
         return rc == GICP_E_NOMEM ? GICP_E_INVALID : rc;

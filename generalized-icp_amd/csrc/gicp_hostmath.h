@@ -124,6 +124,15 @@ void check_knn_args(const double* queries, int64_t Q, int dim, int k, double max
 void knn_host(const double* xyz, int64_t M, const double* queries, int64_t Q, int dim, int k, double max_distance,
               int64_t* index, double* dist2, int32_t* count);
 
+// statistical outlier removal: the setting's checks, what a stage refuses, the host yardstick
+void check_sor(const gicp_sor& s);
+void check_sor_args(const double* xyz, int64_t N, int dim, const gicp_sor* s, const int64_t* M_out, double (&mn)[3], double (&mx)[3]);
+void check_sor_rows(int64_t m);
+void check_sor_extent(int dim, const double (&mn)[3], const double (&mx)[3]);
+void check_sor_result(double t_mean, int64_t kept, int64_t m, const gicp_sor& s);
+void sor_points_host(const double* xyz, int64_t N, int dim, const gicp_sor* s, double* out_xyz, int64_t* out_index,
+                     double* out_mean, double* out_stats, int64_t* M_out);
+
 // registration report: information matrix of a pass's statistics, symmetric eigensolver
 void information(int dim, const double* stats, const double* T, double* H, double* b);
 void sym_eig(int n, const double* A, double* w, double* V);

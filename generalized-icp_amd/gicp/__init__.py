@@ -23,7 +23,8 @@ from ._lib import Debug, Params, Report, ReportSpec, Result, Trace, check, dptr
 
 __all__ = ["gicp", "apply_transformation", "Engine", "RotatedCovariances", "expand_stats", "stats_size",
            "default_params", "last_result", "voxel_downsample", "filter_points", "filter_points_host", "deskew", "deskew_host", "motion_twist", "information",
-           "sym_eig", "align_batch", "multistart", "batch_max_points", "pick_start", "knn", "knn_host", "knn_max_k"]
+           "sym_eig", "align_batch", "multistart", "batch_max_points", "pick_start", "knn", "knn_host", "knn_max_k", "sor_points", "sor_points_host",
+           "sor_max_k"]
 
 
 def stats_size(dim):
@@ -131,6 +132,7 @@ class Engine:
         self._hook_fn = None       # (fn, nranks, rank) of that hook, to restore it after a gicp() call
         self.voxel = (0.0, 1)      # (voxel_size, min_points) of set_voxel; size 0: no filter
         self.filter = _NO_FILTER   # the keywords of set_filter in force (all zero: no filter)
+        self.sor = (0, 0.0)        # (k, std_ratio) of set_sor; k 0: off
         self.map_dim = None        # dimension of the local voxel map (map_reset)
 
     def close(self):
@@ -296,7 +298,25 @@ class Engine:
 
     def _reduces(self):
         """A filter of the builds is in force (set_voxel, set_filter): a cloud then holds fewer rows than its input."""
-        return self.voxel[0] > 0 or _filter_on(self.filter)
+        return self.voxel[0] > 0 or _filter_on(self.filter) or self.sor[0] > 0
+
+    def set_sor(self, k, std_ratio=1.0):
+        """Statistical outlier removal of every cloud set or staged from now on (gicp_set_sor), on the
+        device, after the input filters and before the voxel filter: a row is kept iff the mean distance to its k
+        nearest neighbours is at most mu + std_ratio sigma, mu and sigma the mean and the sample deviation of those
+        means over the cloud (gicp.sor_points has the definition).  k None or 0 turns it off.  With it, every
+        per-point output of this engine refers to the rows of the FILTERED clouds, which points() returns: the
+        input's rows that survive, in their order.  Engine.sor holds the setting as (k, std_ratio)."""
+        k = 0 if k is None else int(k)
+        s = _lib.Sor(k, 0, float(std_ratio) if k else 0.0)
+        check(self._lib.gicp_set_sor(self._ctx, C.byref(s)), self._ctx, "gicp_set_sor")
+        self.sor = (s.k, s.std_ratio)
+
+    def sor_points(self, points, k, std_ratio=1.0, return_index=False, return_mean=False, return_stats=False):
+        """gicp.sor_points on this engine's GPU (gicp_sor_points); the engine's clouds and settings are untouched."""
+        a = self._cloud(points)
+        return _sor_call(lambda *args: check(self._lib.gicp_sor_points(self._ctx, *args), self._ctx, "gicp_sor_points"),
+                         a, k, std_ratio, return_index, return_mean, return_stats)
 
     def set_filter(self, center=None, min_range=0.0, max_range=0.0, radius=0.0, min_neighbors=1):
         """Input filters of every cloud set or staged from now on (gicp_set_filter), on the device,
@@ -1010,6 +1030,59 @@ def filter_points_host(points, center=None, min_range=0.0, max_range=0.0, radius
     return _filter_call(call, a, f, return_index, return_counts)
 
 
+def _sor_call(call, a, k, std_ratio, return_index, return_mean, return_stats):
+    """One one-shot statistical-outlier-removal call (device or host) on the cloud `a`."""
+    s = _lib.Sor(int(k), 0, float(std_ratio))
+    out = np.empty_like(a)
+    idx = np.empty(a.shape[0], dtype=np.int64) if return_index else None
+    mean = np.empty(a.shape[0], dtype=np.float64) if return_mean else None
+    stats = np.empty(3, dtype=np.float64) if return_stats else None
+    m = C.c_int64()
+    call(dptr(a), a.shape[0], a.shape[1], C.byref(s), dptr(out),
+         idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_index else None,
+         dptr(mean) if return_mean else None, dptr(stats) if return_stats else None, C.byref(m))
+    res = (out[:m.value].copy(),)
+    if return_index:
+        res += (idx[:m.value].copy(),)
+    if return_mean:
+        res += (mean,)
+    if return_stats:
+        res += (dict(mu=float(stats[0]), sigma=float(stats[1]), threshold=float(stats[2])),)
+    return res[0] if len(res) == 1 else res
+
+
+def sor_max_k():
+    """The largest k of `sor_points` (gicp_sor_max_k): knn_max_k() - 1."""
+    return int(_lib.load().gicp_sor_max_k())
+
+
+def sor_points(points, k, std_ratio=1.0, return_index=False, return_mean=False, return_stats=False, device=0):
+    """Statistical outlier removal on the GPU (gicp_sor_points): keep the rows of `points` (N x 2 or
+    N x 3, N >= 2) whose mean distance to their k nearest other rows is at most mu + std_ratio sigma, where mu is the
+    mean and sigma the sample deviation of those means over the cloud.  Defined to the bit (include/gicp_hip.h): fp64,
+    every operation rounded on its own, the mean a sequential sum of the roots of the ascending d2 and one division,
+    mu and sigma from pairwise tree sums in row order, the bound inclusive -- NumPy's restatement gives the same rows.
+    Returns the kept rows in their order; with return_index also their int64 rows in `points`; with return_mean also,
+    per INPUT row, the float64 mean neighbour distance; with return_stats also dict(mu, sigma, threshold).
+    Deterministic.  Raises ValueError for k outside 1..sor_max_k(), a negative or non-finite std_ratio, fewer than 2
+    rows, non-finite input, and a call that leaves no row."""
+    return _engine(int(device)).sor_points(points, k, std_ratio, return_index, return_mean, return_stats)
+
+
+def sor_points_host(points, k, std_ratio=1.0, return_index=False, return_mean=False, return_stats=False):
+    """`sor_points` computed on the host by the same functions over a brute-force search (gicp_sor_points_host; no
+    GPU needed): the CPU yardstick, quadratic in the number of rows."""
+    a = Engine._cloud(points)
+    lib = _lib.load()
+
+    def call(*args):
+        rc = lib.gicp_sor_points_host(*args)
+        if rc != _lib.GICP_OK:   # (host only: the message is the thread's, there is no context)
+            raise ValueError(lib.gicp_last_host_error().decode())
+
+    return _sor_call(call, a, k, std_ratio, return_index, return_mean, return_stats)
+
+
 def _knn_array(a, name):
     a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
     if a.ndim != 2:
@@ -1185,7 +1258,7 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
          devices=None, verbose=True, T0=None, method="plane_to_plane", transformation_epsilon=0.0,
          rotation_epsilon=0.0, euclidean_fitness_epsilon=0.0, mse_relative_epsilon=0.0, voxel_size=None,
          voxel_min_points=1, robust_kernel=None, robust_scale=None, min_range=None, max_range=None, outlier_radius=None,
-         outlier_min_neighbors=1, filter_center=None):
+         outlier_min_neighbors=1, filter_center=None, sor_k=None, sor_std_ratio=1.0):
     """Drop-in for gicp.py:78 — returns the same 7-tuple (gicp.py:174):
 
     (T, all_transformations, initial_source_cov_matrices, target_cov_matrices,
@@ -1230,6 +1303,9 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
       (Engine.set_filter: a range crop about filter_center, None the origin, then radius outlier removal), before
       the voxel filter if voxel_size is given, and every per-point member of the 7-tuple -- the covariance
       arrays, the highest-weight points, all_source_cov_matrices -- refers to the FILTERED clouds.
+    sor_k / sor_std_ratio: sor_k None (default) registers the clouds as given.  Otherwise both clouds pass
+      statistical outlier removal on the device (Engine.set_sor) after the input filters and before the voxel
+      filter, and every per-point member of the 7-tuple refers to the FILTERED clouds.
     robust_kernel / robust_scale: None (default) is plain least squares.  'huber', 'cauchy',
       'geman_mcclure' ('gm') or 'tukey' (or the GICP_ROBUST_* code) weights every accepted
       correspondence of a pass by the kernel's w(s / robust_scale), s = sqrt(r^T W r) the whitened residual
@@ -1279,27 +1355,31 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
     filt = None
     if not (min_range is None and max_range is None and outlier_radius is None):
         filt = _filter_kw(filter_center, min_range, max_range, outlier_radius, outlier_min_neighbors)
-    if voxel_size is None and filt is None:
+    if voxel_size is None and filt is None and sor_k is None:
         _run_ranks(engines, build)
         eng = engines[0]
     else:   # the engines are shared between calls: the settings last for this call's builds only
         prev_voxel = [e.voxel for e in engines]
         prev_filter = [e.filter for e in engines]
+        prev_sor = [e.sor for e in engines]
         try:
             for e in engines:
                 if voxel_size is not None:
                     e.set_voxel(voxel_size, voxel_min_points)
                 if filt is not None:
                     e.set_filter(**filt)
+                if sor_k is not None:
+                    e.set_sor(sor_k, sor_std_ratio)
             _run_ranks(engines, build)
             eng = engines[0]
             # the host side of the loops (highest-weight points, the faithful mode's moved source) works on
             # the clouds the engine registers
             src, tgt = eng.points("source"), eng.points("target")
         finally:
-            for e, v, f in zip(engines, prev_voxel, prev_filter):
+            for e, v, f, s in zip(engines, prev_voxel, prev_filter, prev_sor):
                 e.set_voxel(*v)
                 e.set_filter(**f)
+                e.set_sor(*s)
     target_cov = eng.covariances("target")
     init_src_cov = eng.covariances("source")
     for e in engines[1:]:   # each device computed its own shard's source covariances (NaN elsewhere)

@@ -130,6 +130,15 @@ class Filter(C.Structure):
     ]
 
 
+class Sor(C.Structure):
+    """gicp_sor (include/gicp_hip.h): statistical outlier removal of a cloud; k = 0: off."""
+    _fields_ = [
+        ("k", C.c_int32),
+        ("pad", C.c_int32),
+        ("std_ratio", C.c_double),
+    ]
+
+
 class BatchProblem(C.Structure):
     """gicp_batch_problem (include/gicp_hip.h): one registration of a batch."""
     _fields_ = [
@@ -282,6 +291,12 @@ SIGNATURES = {
                                   _DP, C.POINTER(C.c_int32)]),
     "gicp_knn_host": (C.c_int, [_DP, C.c_int64, _DP, C.c_int64, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_int64), _DP,
                                 C.POINTER(C.c_int32)]),
+    "gicp_sor_max_k": (C.c_int, []),
+    "gicp_sor_points": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.POINTER(Sor), _DP, C.POINTER(C.c_int64), _DP, _DP,
+                                  C.POINTER(C.c_int64)]),
+    "gicp_sor_points_host": (C.c_int, [_DP, C.c_int64, C.c_int, C.POINTER(Sor), _DP, C.POINTER(C.c_int64), _DP, _DP,
+                                       C.POINTER(C.c_int64)]),
+    "gicp_set_sor": (C.c_int, [_VP, C.POINTER(Sor)]),
 }
 
 # gicp_allreduce_fn: int (*)(double* buf, int n, void* user)
@@ -294,11 +309,12 @@ HASH_SRCS = ("csrc/gicp_index.hip", "csrc/gicp_cov.hip", "csrc/gicp_corr.hip", "
              "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
              "csrc/gicp_build.cpp", "csrc/gicp_align.cpp", "csrc/gicp_exchange.cpp", "csrc/gicp_voxel.hip",
              "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_filter.hip", "csrc/gicp_batch.hip", "csrc/gicp_batch.cpp",
-             "csrc/gicp_knn.hip",
+             "csrc/gicp_knn.hip", "csrc/gicp_sor.hip",
              "csrc/gicp_internal.h", "csrc/gicp_mem.h",
              "csrc/gicp_sweep.h", "csrc/gicp_filter.h", "csrc/gicp_cov_dev.h", "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
              "../include/gicp_hip.h",
-             "csrc/gicp_wave_dev.h", "csrc/gicp_search_dev.h", "csrc/gicp_stats_dev.h", "csrc/gicp_bounds_dev.h")
+             "csrc/gicp_wave_dev.h", "csrc/gicp_search_dev.h", "csrc/gicp_stats_dev.h", "csrc/gicp_bounds_dev.h",
+             "csrc/gicp_sor.h")
 
 
 def source_hash():

@@ -40,7 +40,7 @@ class Odometry:
     def __init__(self, dim=3, params=None, device=0, composition="se3", init="constant_velocity", borrow=False,
                  voxel_size=None, voxel_min_points=1, map_voxel_size=None, map_range=None, map_min_points=1,
                  deskew=False, deskew_ref=0.5, report=None, min_range=None, max_range=None, outlier_radius=None,
-                 outlier_min_neighbors=1, **kw):
+                 outlier_min_neighbors=1, sor_k=None, sor_std_ratio=1.0, **kw):
         if composition not in ("se3", "reference"):
             raise ValueError("composition must be 'se3' or 'reference'")
         if init not in ("identity", "constant_velocity"):
@@ -73,6 +73,10 @@ class Odometry:
         # max-range and invalid returns that would stretch the cloud's extent
         if not (min_range is None and max_range is None and outlier_radius is None):
             self.eng.set_filter(None, min_range, max_range, outlier_radius, outlier_min_neighbors)
+        # sor_k / sor_std_ratio: every scan then passes statistical outlier removal on the device (Engine.set_sor),
+        # after those filters and before the voxel filter
+        if sor_k is not None:
+            self.eng.set_sor(sor_k, sor_std_ratio)
         self.composition = composition
         self.init = init
         # borrow=True: staged scans are read by the library in place (GICP_STAGE_BORROW, no copy on this

@@ -163,7 +163,9 @@ int gicp_version(void);                          /* 100 * major + minor; 101: gi
                                                     gicp_filter_points[_host], gicp_set_filter); 105: batched
                                                     registration (gicp_batch_align, gicp_batch_max_points); 106:
                                                     exact k-nearest-neighbour queries (gicp_knn, gicp_knn_points,
-                                                    gicp_knn_host, gicp_knn_max_k) */
+                                                    gicp_knn_host, gicp_knn_max_k); 107: statistical outlier
+                                                    removal (gicp_sor, gicp_sor_points[_host], gicp_set_sor,
+                                                    gicp_sor_max_k) */
 int gicp_stats_size(int dim);                    /* 26 (dim 2) or 74 (dim 3) */
 void gicp_default_params(int dim, gicp_params* out);
 const char* gicp_strerror(int code);
@@ -209,10 +211,10 @@ int gicp_peer_close(gicp_ctx* ctx);   /* back to no exchange (RCCL / hook as set
 /* Build provenance of this library: "src=<first 16 hex of sha256 over the sources>;git=<rev>;built=<date
  * time>;arch=gfx950".  The source hash covers csrc/{gicp_index.hip, gicp_cov.hip, gicp_corr.hip, gicp_extras.hip,
  * gicp_capi.cpp, gicp_solver.cpp, gicp_cg.cpp, gicp_hostmath.cpp, gicp_build.cpp, gicp_align.cpp, gicp_exchange.cpp,
- * gicp_voxel.hip, gicp_sweep.hip, gicp_eval.hip, gicp_filter.hip, gicp_batch.hip, gicp_batch.cpp, gicp_internal.h,
+ * gicp_voxel.hip, gicp_sweep.hip, gicp_eval.hip, gicp_filter.hip, gicp_batch.hip, gicp_batch.cpp, gicp_knn.hip, gicp_sor.hip, gicp_internal.h,
  * gicp_mem.h, gicp_sweep.h, gicp_filter.h, gicp_cov_dev.h, gicp_solver.h, gicp_solve_dev.h, gicp_hostmath.h,
  * gicp_host.h}, include/gicp_hip.h and csrc/{gicp_wave_dev.h, gicp_search_dev.h, gicp_stats_dev.h,
- * gicp_bounds_dev.h}, concatenated in that order (the Makefile's SRCS, then its HEADERS), so
+ * gicp_bounds_dev.h, gicp_sor.h}, concatenated in that order (the Makefile's SRCS, then its HEADERS), so
  * a caller can prove the loaded library was compiled from the sources beside it. */
 const char* gicp_build_info(void);
 
@@ -497,7 +499,7 @@ int gicp_filter_points(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, con
                        int64_t* out_index, int32_t* out_count, int64_t* M_out);
 int gicp_filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz,
                             int64_t* out_index, int32_t* out_count, int64_t* M_out);
-const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host or gicp_knn_host, or refused gicp_batch_align ("" if none) */
+const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host, gicp_knn_host or gicp_sor_points_host, or refused gicp_batch_align ("" if none) */
 int gicp_set_filter(gicp_ctx* ctx, const gicp_filter* f);
 
 /* ---- local voxel map ----------------------------------------------------------------
@@ -705,6 +707,63 @@ int gicp_knn_points(gicp_ctx* ctx, const double* xyz, int64_t M, const double* q
                     double max_distance, int64_t* index, double* dist2, int32_t* count);
 int gicp_knn_host(const double* xyz, int64_t M, const double* queries, int64_t Q, int dim, int k, double max_distance,
                   int64_t* index, double* dist2, int32_t* count);
+
+/* ---- statistical outlier removal -----------------------------------------------------
+ * Removes the rows whose mean distance to their k nearest neighbours is large against the cloud's own statistic
+ * (PCL's StatisticalOutlierRemoval, Open3D's remove_statistical_outlier), defined to the bit.
+ * Input: M >= 2 rows, finite, dim 2 or 3, and a gicp_sor with k in 1 .. gicp_sor_max_k() (= gicp_knn_max_k() - 1
+ * = 31) and std_ratio finite and >= 0.
+ * Every operation below is fp64 and rounded on its own: no FMA, a correctly rounded sqrt, a correctly rounded
+ * division.
+ *   1. MEAN NEIGHBOUR DISTANCE.  n_i = min(k, M - 1).  Take the n_i smallest values of d2(p_i, p_j) over j != i,
+ *      d2 the expression of the k-nearest-neighbour queries above; coincident other rows count, at 0.
+ *      mean_i = (sum of sqrt(d2)) / n_i, the sum sequential in ascending order of d2, then one division.  Only the
+ *      multiset of d2 values enters, so the result does not depend on how exact ties are ordered.  (On the device: a
+ *      self-query for k + 1 rows with entry 0 dropped -- entry 0 is always a zero, the row itself or a coincident
+ *      row of lower index.)
+ *   2. TREE SUM T(v) of a vector in original row order: pad with +0.0 to the next power of two, replace v by
+ *      v[0::2] + v[1::2] until one value is left.  All summands here are >= 0, so padding equals carrying the odd
+ *      element.  (A wave's xor-butterfly over 64 consecutive rows, then (w0 + w1) + (w2 + w3) per 256 aligned rows,
+ *      then the same tree over the partials, is this tree.)
+ *   3. CLOUD STATISTICS.  mu = T(mean) / M;  dev_i = mean_i - mu;  sigma = sqrt(T(dev_i * dev_i) / (M - 1)) -- the
+ *      two-pass sample deviation.
+ *   4. DECISION.  thr = mu + std_ratio * sigma, the product first.  Keep i iff mean_i <= thr: the bound is
+ *      inclusive, like every bound in this library.  One pass, not iterated.  Survivors keep their relative order.
+ * The same functions (csrc/gicp_sor.h) serve the device kernels and gicp_sor_points_host.  No floating-point
+ * atomics: the output is bit-identical from call to call, context to context, and to the host's.
+ * GICP_E_INVALID, with the stage named in the message ("sor: ..."), for: k out of range; std_ratio negative or not
+ * finite; M < 2; non-finite input; a T(mean) that is not finite; a stage that leaves no row (possible with
+ * std_ratio = 0 when all means are equal and mu rounds below them).  Rows whose bounding box has a squared diagonal
+ * that fp64 does not hold (coordinates about 1e154 apart) are refused before anything runs, by the device and the
+ * host function alike: only there can a d2 overflow, so T(mean) is finite for every cloud that passes.
+ *
+ * One-shot, host in, host out (gicp_sor_points): out_xyz [N][dim], out_index [N], out_mean [N] (per INPUT row) and
+ * out_stats [3] (mu, sigma, thr) are caller-allocated and any of them may be NULL; *M_out receives the number of
+ * rows kept (they come first in out_xyz and out_index; out_index: the original row of each, ascending).  The
+ * context's clouds and settings are untouched.  gicp_sor_points_host is host only (no HIP call, no context): a
+ * brute force through the same search as gicp_knn_host, the CPU yardstick; its message is gicp_last_host_error()'s.
+ *
+ * Context setting (gicp_set_sor; NULL or k = 0: off, the default): every later cloud build runs
+ *   upload -> de-skew -> crop -> radius outlier removal -> STATISTICAL OUTLIER REMOVAL -> voxel filter -> index
+ * on the device.  The stage works on the survivors of the stages before it (M above is their number, "original
+ * row order" theirs) and hands the next stage its survivors and their exact bounds on the device; it costs one
+ * stream synchronisation beyond those of its own index build, and only result words return to the host.  A staged
+ * build uses the setting in force when it was staged, on its own stream and scratch; GICP_STAGE_BORROW still reads
+ * the caller's frame in place.  With a sharded source every rank filters the whole cloud.  A failure after the
+ * build began leaves that cloud NOT SET.  "Original order" of a cloud means the rows of the filtered cloud, as for
+ * the other filters.  With the setting off a build is what it was without this section. */
+typedef struct gicp_sor {
+    int32_t k;         /* neighbours of the mean, 1 .. gicp_sor_max_k(); 0: off (gicp_set_sor only) */
+    int32_t pad;
+    double std_ratio;  /* finite, >= 0 */
+} gicp_sor;
+int gicp_sor_max_k(void);   /* 31 */
+int gicp_sor_points(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, const gicp_sor* s, double* out_xyz,
+                    int64_t* out_index, double* out_mean /* [N], per input row */,
+                    double* out_stats /* [3]: mu, sigma, thr */, int64_t* M_out);
+int gicp_sor_points_host(const double* xyz, int64_t N, int dim, const gicp_sor* s, double* out_xyz, int64_t* out_index,
+                         double* out_mean, double* out_stats, int64_t* M_out);
+int gicp_set_sor(gicp_ctx* ctx, const gicp_sor* s);
 
 #ifdef __cplusplus
 }

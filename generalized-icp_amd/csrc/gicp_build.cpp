@@ -401,6 +401,73 @@ FilterOut sor_stage(BuildScratch& bs, const double* d_in, int64_t m, int dim, co
     return fo;
 }
 
+// Euclidean cluster extraction (gicp_cluster.hip) of the device cloud d_in [m][dim] with bounds mn /
+// mx: the grid of radius outlier removal at edge c.radius, the components in one pass, labels, sizes and the decision,
+// the compaction of the kept clusters' rows into d_out (never d_in).  track: also the input row of each survivor.
+// The labels stay in bs.c_labels, the sizes in bs.c_sizes.  One stream sync; the result words (bounds, M, C) are all
+// that returns.
+FilterOut cluster_stage(BuildScratch& bs, const double* d_in, int64_t m, int dim, const double (&mn)[3], const double (&mx)[3],
+                        const gicp_cluster& c, double* d_out, bool track, int64_t* n_clusters, BuildLog& log, hipStream_t st) {
+    VoxelArgs va{};
+    ClusterArgs ca{};
+    va.raw = d_in;
+    va.n = m;
+    va.dim = dim;
+    va.min_points = 1;
+    va.end_bit = ror_key_bits(dim, mn, mx, c.radius, va.leaf, va.cmin, va.bits, ca.cmax, "cluster");
+    bs.v_keys.reserve((size_t)m);
+    bs.v_keys2.reserve((size_t)m);
+    bs.v_idx.reserve((size_t)m);
+    bs.v_idx2.reserve((size_t)m);
+    bs.f_packed.reserve((size_t)m * dim);
+    bs.f_keep.reserve((size_t)m);
+    bs.f_pos.reserve((size_t)m);
+    bs.c_parent.reserve((size_t)m);
+    bs.c_size.reserve((size_t)m);
+    bs.c_root.reserve((size_t)m);
+    bs.c_cid.reserve((size_t)m);
+    bs.c_labels.reserve((size_t)m);
+    bs.c_sizes.reserve((size_t)m);
+    if (track) bs.c_rows.reserve((size_t)m);
+    if (!bs.v_res) bs.v_res.alloc((size_t)kVoxelRes);
+    size_t tmp_bytes = 0;
+    HIPCHK(voxel_temp_bytes(m, va.end_bit, &tmp_bytes, st));
+    bs.v_tmp.reserve(tmp_bytes + 16);
+    va.keys = bs.v_keys;
+    va.keys_s = bs.v_keys2;
+    va.idx = bs.v_idx;
+    va.idx_s = bs.v_idx2;
+    va.tmp = bs.v_tmp;
+    va.tmp_bytes = tmp_bytes;
+    va.res = bs.v_res;
+    ca.r2 = c.radius * c.radius;
+    ca.min_size = c.min_size;
+    ca.max_size = c.max_size;
+    ca.packed = bs.f_packed;
+    ca.parent = bs.c_parent;
+    ca.size = bs.c_size;
+    ca.root = bs.c_root;
+    ca.cid1 = bs.c_cid;
+    ca.labels = bs.c_labels;
+    ca.sizes = bs.c_sizes;
+    ca.keep = bs.f_keep;
+    ca.pos1 = bs.f_pos;
+    ca.out = d_out;
+    ca.idx_out = track ? bs.c_rows.get() : nullptr;
+    HIPCHK(launch_cluster(va, ca, st));
+    unsigned long long res[kVoxelRes];
+    read_result_words(bs, res, st);
+    log.tick("cluster");
+    FilterOut fo;
+    fo.M = (int64_t)res[6];
+    check_cluster_result(fo.M, m, (int64_t)res[7], c);
+    decode_bounds(res, dim, fo.mn, fo.mx);
+    fo.pts = d_out;
+    fo.idx = ca.idx_out;
+    if (n_clusters) *n_clusters = (int64_t)res[7];
+    return fo;
+}
+
 // The core of a cloud build: the index (build_index), then covariances and (graph) the neighbour graph.
 void build_core(Cloud& cl, int64_t n, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_params& p,
                 BuildScratch& bs, const BuildSpec& spec, BuildLog& log) {
@@ -580,23 +647,29 @@ void build_cloud(Cloud& cl, const double* xyz, int64_t n, int dim, const gicp_pa
         log.tick("deskew");
     };
     // (a staged build passes its pinned copy: the H2D copy is then asynchronous)
-    const bool sor = spec.sor.k > 0;
-    if (filter_on(spec.filter) || sor) {
-        // upload, de-skew, crop, radius outlier removal, statistical outlier removal, voxel filter, index: every
-        // stage hands the next one its survivors and their exact bounds on the device; the last input filter writes
-        // where the index reads
+    const bool sor = spec.sor.k > 0, cluster = spec.cluster.radius > 0.0;
+    if (filter_on(spec.filter) || sor || cluster) {
+        // upload, de-skew, crop, radius outlier removal, statistical outlier removal, cluster extraction, voxel filter,
+        // index: every stage hands the next one its survivors and their exact bounds on the device; the last input
+        // filter writes where the index reads
         const bool voxel = spec.voxel_leaf > 0.0;
         bs.v_raw.reserve((size_t)n * dim);
         HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * n * dim, hipMemcpyHostToDevice, st));
         log.tick("upload");
         if (spec.sweep) deskew(bs.v_raw);
-        FilterOut fo = filter_stages(bs, bs.v_raw, n, dim, mn, mx, spec.filter, voxel || sor ? nullptr : bs.s_in.get(), false,
-                                     nullptr, st);
+        FilterOut fo = filter_stages(bs, bs.v_raw, n, dim, mn, mx, spec.filter, voxel || sor || cluster ? nullptr : bs.s_in.get(),
+                                     false, nullptr, st);
         log.tick("filter");
         if (sor) {
-            if (voxel) bs.o_pts.reserve((size_t)fo.M * dim);
-            fo = sor_stage(bs, fo.pts, fo.M, dim, fo.mn, fo.mx, spec.sor, voxel ? bs.o_pts.get() : bs.s_in.get(), false, nullptr,
+            const bool more = voxel || cluster;
+            if (more) bs.o_pts.reserve((size_t)fo.M * dim);
+            fo = sor_stage(bs, fo.pts, fo.M, dim, fo.mn, fo.mx, spec.sor, more ? bs.o_pts.get() : bs.s_in.get(), false, nullptr,
                            log, st);
+        }
+        if (cluster) {
+            if (voxel) bs.c_pts.reserve((size_t)fo.M * dim);
+            fo = cluster_stage(bs, fo.pts, fo.M, dim, fo.mn, fo.mx, spec.cluster, voxel ? bs.c_pts.get() : bs.s_in.get(), false,
+                               nullptr, log, st);
         }
         n = fo.M;
         for (int a = 0; a < 3; ++a) mn[a] = fo.mn[a], mx[a] = fo.mx[a];
@@ -629,6 +702,7 @@ BuildSpec target_spec(const gicp_ctx* c, hipStream_t st) {
     spec.voxel_min = c->voxel_min;
     spec.filter = c->filt;
     spec.sor = c->sor;
+    spec.cluster = c->cluster;
     spec.stream = st;
     return spec;
 }
@@ -643,6 +717,7 @@ BuildSpec source_spec(const gicp_ctx* c, int shard, int nshards) {
     spec.voxel_min = c->voxel_min;
     spec.filter = c->filt;
     spec.sor = c->sor;
+    spec.cluster = c->cluster;
     spec.stream = c->stream;
     return spec;
 }
@@ -752,6 +827,33 @@ void sor_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const double
     if (out_stats)
         for (int a = 0; a < 3; ++a) out_stats[a] = stats[a];
     *M_out = fo.M;
+}
+
+// gicp_cluster_points: the one-shot of Euclidean cluster extraction, host in, host out; every output may be null.
+// The stage's synchronisation brings the result words; a decision that keeps no row is refused there, before any
+// output is written.
+void cluster_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const double (&mn)[3], const double (&mx)[3],
+                    const gicp_cluster& cl, int32_t* labels, int32_t* sizes, int64_t* n_clusters, double* out_xyz, int64_t* out_index,
+                    int64_t* M_out) {
+    BuildScratch& bs = c->bs;
+    hipStream_t st = c->stream;
+    bs.v_raw.reserve((size_t)N * dim);
+    bs.c_pts.reserve((size_t)N * dim);
+    HIPCHK(hipMemcpyAsync(bs.v_raw, xyz, sizeof(double) * N * dim, hipMemcpyHostToDevice, st));
+    BuildLog log(st);
+    log.verbose = false;   // (nothing prints a one-shot's phases: no synchronisation for them)
+    int64_t C = 0;
+    const FilterOut fo = cluster_stage(bs, bs.v_raw, N, dim, mn, mx, cl, bs.c_pts, out_index != nullptr, &C, log, st);
+    std::vector<int32_t> idx(out_index ? (size_t)fo.M : 0);
+    if (labels) HIPCHK(hipMemcpyAsync(labels, bs.c_labels, sizeof(int32_t) * N, hipMemcpyDeviceToHost, st));
+    if (sizes) HIPCHK(hipMemcpyAsync(sizes, bs.c_sizes, sizeof(int32_t) * C, hipMemcpyDeviceToHost, st));
+    if (out_xyz) HIPCHK(hipMemcpyAsync(out_xyz, fo.pts, sizeof(double) * fo.M * dim, hipMemcpyDeviceToHost, st));
+    if (out_index) HIPCHK(hipMemcpyAsync(idx.data(), fo.idx, sizeof(int32_t) * fo.M, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (out_index)
+        for (int64_t m = 0; m < fo.M; ++m) out_index[m] = idx[m];
+    if (n_clusters) *n_clusters = C;
+    if (M_out) *M_out = fo.M;
 }
 
 // gicp_knn / gicp_knn_points: the k nearest database rows of every query, host out.  The database

@@ -82,7 +82,7 @@ void check_sweep_args(const double* xyz, const double* stamps, int64_t N, int di
 
 extern "C" {
 
-int gicp_version(void) { return 107; }
+int gicp_version(void) { return 108; }
 
 int gicp_stats_size(int dim) { return (dim == 2 || dim == 3) ? nstat(dim == 2 ? 2 : 3) : GICP_E_INVALID; }
 
@@ -555,6 +555,30 @@ int gicp_sor_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gi
         double mn[3], mx[3];
         check_sor_args(xyz, N, dim, s, M_out, mn, mx);   // (the one scan of the cloud: finiteness and bounds)
         sor_points(c, xyz, N, dim, mn, mx, *s, out_xyz, out_index, out_mean, out_stats, M_out);
+    });
+}
+
+// ---- Euclidean cluster extraction; gicp_cluster_points_host lives in gicp_hostmath.cpp ----
+
+int gicp_set_cluster(gicp_ctx* c, const gicp_cluster* cl) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_set_cluster", [&] {
+        gicp_cluster v{};
+        if (cl && cl->radius != 0.0) {
+            check_cluster(*cl);
+            v = *cl;
+        }
+        c->cluster = v;
+    });
+}
+
+int gicp_cluster_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gicp_cluster* cl, int32_t* labels, int32_t* sizes,
+                        int64_t* n_clusters, double* out_xyz, int64_t* out_index, int64_t* M_out) {
+    if (!c) return GICP_E_INVALID;
+    return guard_impl(c, "gicp_cluster_points", [&] {
+        double mn[3], mx[3];
+        check_cluster_args(xyz, N, dim, cl, mn, mx);   // (the one scan of the cloud: finiteness and bounds)
+        cluster_points(c, xyz, N, dim, mn, mx, *cl, labels, sizes, n_clusters, out_xyz, out_index, M_out);
     });
 }
 

@@ -27,6 +27,7 @@
 #include "gicp_bounds_dev.h"
 #include "gicp_filter.h"
 #include "gicp_internal.h"
+#include "gicp_runs_dev.h"
 
 namespace gicp {
 
@@ -92,19 +93,6 @@ __global__ void __launch_bounds__(256) k_ror_gather(const double* __restrict__ i
     for (int a = 0; a < D; ++a) packed[j * D + a] = in[o * D + a];
 }
 
-// first sorted key >= k (Upper: > k) in ks[0 .. n)
-template <bool Upper>
-__device__ __forceinline__ int64_t key_bound(const uint64_t* __restrict__ ks, int64_t n, uint64_t k) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        const uint64_t v = ks[mid];
-        if (Upper ? v <= k : v < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // One lane per point in key order.  Full = false: a lane stops at min_neighbors (its count is then a lower
 // bound that decides the same keep flag).
 template <int D, bool Full>
@@ -116,35 +104,17 @@ __global__ void __launch_bounds__(256) k_ror_count(VoxelArgs V, RorArgs R) {
     const uint64_t key = ks[j];
     double p[D];
     for (int a = 0; a < D; ++a) p[a] = pk[j * D + a];
-    // the cells, relative to cmin: the last axis in the low bits
-    const int bl = V.bits[D - 1], bm = D == 3 ? V.bits[1] : 0;
-    const int64_t cl = (int64_t)(key & ((1ull << bl) - 1ull));
-    const int64_t cm = D == 3 ? (int64_t)((key >> bl) & ((1ull << bm) - 1ull)) : 0;
-    const int64_t ch = (int64_t)(key >> (bl + bm));
-    const int64_t l0 = cl > 0 ? cl - 1 : 0, l1 = cl < R.cmax[D - 1] ? cl + 1 : cl;   // (clipped at the axis ends)
     int32_t count = 0;
-    bool done = false;
-    for (int dh = -1; dh <= 1 && !done; ++dh) {
-        const int64_t h = ch + dh;
-        if (h < 0 || h > R.cmax[0]) continue;
-        for (int dm = (D == 3 ? -1 : 0); dm <= (D == 3 ? 1 : 0) && !done; ++dm) {
-            const int64_t m = cm + dm;
-            if (D == 3 && (m < 0 || m > R.cmax[1])) continue;
-            const uint64_t row = (((uint64_t)h << bm) | (uint64_t)m) << bl;
-            const int64_t b = key_bound<false>(ks, V.n, row | (uint64_t)l0);
-            const int64_t e = key_bound<true>(ks, V.n, row | (uint64_t)l1);
-            for (int64_t t = b; t < e; ++t) {
-                if (t == j) continue;
-                double q[D];
-                for (int a = 0; a < D; ++a) q[a] = pk[t * D + a];
-                count += ror_near(filter_d2<D>(p, q), R.r2) ? 1 : 0;
-                if (!Full && count >= R.min_neighbors) {
-                    done = true;
-                    break;
-                }
-            }
+    neighbour_runs<D, false>(ks, V.n, key, V.bits, R.cmax, [&](int64_t b, int64_t e) {
+        for (int64_t t = b; t < e; ++t) {
+            if (t == j) continue;
+            double q[D];
+            for (int a = 0; a < D; ++a) q[a] = pk[t * D + a];
+            count += ror_near(filter_d2<D>(p, q), R.r2) ? 1 : 0;
+            if (!Full && count >= R.min_neighbors) return true;
         }
-    }
+        return false;
+    });
     const int64_t o = V.idx_s[j];
     R.keep[o] = count >= R.min_neighbors ? 1 : 0;
     if (Full && R.cnt_out) R.cnt_out[R.idx_in ? R.idx_in[o] : o] = count;
@@ -161,16 +131,24 @@ hipError_t compact(const double* in, int64_t n, int32_t* keep, int32_t* pos1, vo
     return hipGetLastError();
 }
 
+// The grid both neighbour stages walk: keys of V.raw's rows, (key, row) sorted, the points packed in key order
+template <int D>
+hipError_t grid_sort(const VoxelArgs& V, double* packed, hipStream_t st) {
+    hipError_t e = launch_voxel_keys(V, st);   // (also resets the result words)
+    if (e != hipSuccess) return e;
+    size_t tb = V.tmp_bytes;
+    e = rocprim::radix_sort_pairs(V.tmp, tb, V.keys, V.keys_s, V.idx, V.idx_s, (size_t)V.n, 0u, (unsigned)V.end_bit, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ror_gather<D>, dim3(grid256(V.n)), dim3(256), 0, st, V.raw, (const int32_t*)V.idx_s, V.n, packed);
+    return hipGetLastError();
+}
+
 template <int D>
 hipError_t ror(const VoxelArgs& V, const RorArgs& R, hipStream_t st) {
     const int64_t n = V.n;
     const unsigned g = grid256(n);
-    hipError_t e = launch_voxel_keys(V, st);   // (also resets the result words)
+    hipError_t e = grid_sort<D>(V, R.packed, st);
     if (e != hipSuccess) return e;
-    size_t tb = V.tmp_bytes;
-    e = rocprim::radix_sort_pairs(V.tmp, tb, V.keys, V.keys_s, V.idx, V.idx_s, (size_t)n, 0u, (unsigned)V.end_bit, st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_ror_gather<D>, dim3(g), dim3(256), 0, st, V.raw, (const int32_t*)V.idx_s, n, R.packed);
     if (R.full) hipLaunchKernelGGL((k_ror_count<D, true>), dim3(g), dim3(256), 0, st, V, R);
     else hipLaunchKernelGGL((k_ror_count<D, false>), dim3(g), dim3(256), 0, st, V, R);
     e = hipGetLastError();
@@ -210,6 +188,19 @@ hipError_t launch_filter_compact(const double* in, int64_t n, int dim, int32_t* 
     if (n <= 0 || (dim != 2 && dim != 3) || !in || !out || !keep || !pos1 || !res) return hipErrorInvalidValue;
     return dim == 3 ? compact<3>(in, n, keep, pos1, tmp, tmp_bytes, idx_in, out, idx_out, res, st)
                     : compact<2>(in, n, keep, pos1, tmp, tmp_bytes, idx_in, out, idx_out, res, st);
+}
+
+// ... and the steps before and between for Euclidean cluster extraction (gicp_cluster.hip): the sorted grid of
+// radius outlier removal (keys, sort, k_ror_gather; the result words are reset), and the scan alone
+hipError_t launch_grid_sort(const VoxelArgs& V, double* packed, hipStream_t st) {
+    if (V.n <= 0 || (V.dim != 2 && V.dim != 3) || V.end_bit < 1 || V.end_bit > 64 || !V.raw || !packed || !V.res) return hipErrorInvalidValue;
+    return V.dim == 3 ? grid_sort<3>(V, packed, st) : grid_sort<2>(V, packed, st);
+}
+
+hipError_t launch_flag_scan(const int32_t* flags, int32_t* pos1, int64_t n, void* tmp, size_t tmp_bytes, hipStream_t st) {
+    if (n <= 0 || !flags || !pos1) return hipErrorInvalidValue;
+    size_t tb = tmp_bytes;
+    return rocprim::inclusive_scan(tmp, tb, flags, pos1, (size_t)n, rocprim::plus<int32_t>(), st);
 }
 
 }  // namespace gicp

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <memory>
 
+#include "gicp_cluster.h"
 #include "gicp_filter.h"
 #include "gicp_hostmath.h"
 #include "gicp_sor.h"
@@ -47,6 +48,7 @@ hipError_t launch_batch_align(const BatchArgs&, int, int, hipStream_t);
 int batch_max_points(int dim);
 hipError_t launch_knn_query(const KnnArgs&, hipStream_t);
 hipError_t launch_sor(const SorArgs&, hipStream_t);
+hipError_t launch_cluster(const VoxelArgs&, const ClusterArgs&, hipStream_t);
 size_t sor_part_count(int64_t n);
 int corr_grid(int q_tiles, int shard, int nshards);
 int solve_pose(int d, const double* st, const double* Tk, double* Tout, double* loss_out);
@@ -175,6 +177,11 @@ struct BuildScratch {
     DevBuf<int64_t> o_idx;
     DevBuf<double> o_d2, o_mean, o_part, o_stats, o_pts;
     DevBuf<int32_t> o_cnt, o_rows;
+    // Euclidean cluster extraction (gicp_cluster.hip): the forest, the sizes by root, the root flags
+    // and their scan, labels and sizes by cluster, the survivors and their rows; keys, sort, packed points, keep
+    // flags and result words are the input filters'
+    DevBuf<int32_t> c_parent, c_size, c_root, c_cid, c_labels, c_sizes, c_rows;
+    DevBuf<double> c_pts;
     std::unique_ptr<WorkerPool> pool;  // tiling threads (lazily started)
     WorkerPool& workers() {
         if (!pool) {
@@ -217,6 +224,9 @@ struct BuildSpec {
     gicp_filter filter{};
     // statistical outlier removal, run after the input filters and before the voxel filter; k = 0: off
     gicp_sor sor{};
+    // Euclidean cluster extraction, run after statistical outlier removal and before the voxel filter;
+    // radius = 0: off
+    gicp_cluster cluster{};
     // sweep: the uploaded cloud is first de-skewed on the device, point i moved by
     // Exp((stamps[i] - ref) Log(motion)); the filter and the index then see the de-skewed points and their bounds.
     // The twist is taken from `motion` ((dim+1)^2 row-major) once the build has begun, so a motion it refuses
@@ -303,6 +313,7 @@ struct gicp_ctx {
     int voxel_min = 1;
     gicp_filter filt{};               // input filters of every later cloud build (gicp_set_filter): all-zero = off
     gicp_sor sor{};                   // statistical outlier removal of every later cloud build (gicp_set_sor): k = 0 = off
+    gicp_cluster cluster{};           // cluster extraction of every later cloud build (gicp_set_cluster): radius = 0 = off
     gicp::VoxelMap map;               // local voxel map (gicp_map_reset)
     // staged targets (gicp_stage_target / gicp_commit_target): a ring of GICP_MAX_STAGED slots, each
     // built into its own cloud on its own stream by a host thread while the current target is
@@ -419,6 +430,9 @@ void filter_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const gic
                    int32_t* out_count, int64_t* M_out);
 void sor_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const double (&mn)[3], const double (&mx)[3], const gicp_sor& s,
                 double* out_xyz, int64_t* out_index, double* out_mean, double* out_stats, int64_t* M_out);
+void cluster_points(gicp_ctx* c, const double* xyz, int64_t N, int dim, const double (&mn)[3], const double (&mx)[3],
+                    const gicp_cluster& cl, int32_t* labels, int32_t* sizes, int64_t* n_clusters, double* out_xyz, int64_t* out_index,
+                    int64_t* M_out);
 void deskew_cloud(gicp_ctx* c, const double* xyz, const double* stamps, int64_t N, int dim, const double* xi, double ref,
                   double* out);
 void knn_query(gicp_ctx* c, const Cloud* resident, const double* xyz, int64_t M, const double* queries, int64_t Q, int dim,

@@ -9,6 +9,7 @@
 #include <new>
 #include <type_traits>
 
+#include "gicp_cluster.h"
 #include "gicp_filter.h"
 #include "gicp_sor.h"
 #include "gicp_sweep.h"
@@ -445,9 +446,10 @@ void fail_filter_empty(int stage, int64_t n, const gicp_filter& f) {
 
 // The grid of radius outlier removal over the cropped cloud's bounds.  The limit is stated in cells of edge
 // `radius`; the keys are those of the voxel filter's grid with leaf = radius kRorEdge (gicp_filter.h), which spans
-// no more cells.  Returns the bits the sort covers; cmax: the highest cell per axis relative to cmin.
+// no more cells.  Returns the bits the sort covers; cmax: the highest cell per axis relative to cmin.  stage: the
+// stage a refusal names ("filter"; "cluster" for Euclidean cluster extraction, which walks the same grid).
 int ror_key_bits(int dim, const double (&mn)[3], const double (&mx)[3], double radius, double& leaf, double (&cmin)[3],
-                 int32_t (&bits)[3], int64_t (&cmax)[3]) {
+                 int32_t (&bits)[3], int64_t (&cmax)[3], const char* stage) {
     const double lim = dim == 3 ? 2097152.0 : 2147483648.0;   // 2^21, 2^31 cells per axis
     for (int a = 0; a < dim; ++a) {
         const double c0 = std::floor(mn[a] / radius), c1 = std::floor(mx[a] / radius);
@@ -455,13 +457,13 @@ int ror_key_bits(int dim, const double (&mn)[3], const double (&mx)[3], double r
         char b[224];
         if (!(range <= lim)) {
             std::snprintf(b, sizeof b,
-                          "filter: radius grid too wide: axis %c spans %.6g cells of edge radius = %g (at most 2^%d per axis in "
+                          "%s: radius grid too wide: axis %c spans %.6g cells of edge radius = %g (at most 2^%d per axis in "
                           "%d-D); crop the far returns first with a max_range",
-                          "xyz"[a], range, radius, dim == 3 ? 21 : 31, dim);
+                          stage, "xyz"[a], range, radius, dim == 3 ? 21 : 31, dim);
             throw Fail{GICP_E_INVALID, b};
         }
         if (!(std::fabs(c0) < 34359738368.0 && std::fabs(c1) < 34359738368.0)) {   // 2^35: see kRorEdge
-            std::snprintf(b, sizeof b, "filter: axis %c lies beyond 2^35 cells of edge radius = %g from the origin", "xyz"[a],
+            std::snprintf(b, sizeof b, "%s: axis %c lies beyond 2^35 cells of edge radius = %g from the origin", stage, "xyz"[a],
                           radius);
             throw Fail{GICP_E_INVALID, b};
         }
@@ -473,6 +475,44 @@ int ror_key_bits(int dim, const double (&mn)[3], const double (&mx)[3], double r
 }
 
 namespace {
+
+// f(b, e) for every run [b, e) of the sorted (key, row) pairs that holds neighbour cells of the cell of `key`: the
+// device's runs (gicp_runs_dev.h), clipped at the ends of the last axis, rows of cells outside the grid skipped
+template <int D, class F>
+void host_runs(const std::vector<std::pair<uint64_t, int64_t>>& ks, uint64_t key, const int32_t (&bits)[3], const int64_t (&cmax)[3],
+               F&& f) {
+    const int bl = bits[D - 1], bm = D == 3 ? bits[1] : 0;
+    auto first = [&](uint64_t k) { return std::lower_bound(ks.begin(), ks.end(), std::make_pair(k, (int64_t)-1)) - ks.begin(); };
+    const int64_t cl = (int64_t)(key & ((1ull << bl) - 1ull));
+    const int64_t cm = D == 3 ? (int64_t)((key >> bl) & ((1ull << bm) - 1ull)) : 0;
+    const int64_t ch = (int64_t)(key >> (bl + bm));
+    const int64_t l0 = cl > 0 ? cl - 1 : 0, l1 = cl < cmax[D - 1] ? cl + 1 : cl;
+    for (int dh = -1; dh <= 1; ++dh) {
+        const int64_t h = ch + dh;
+        if (h < 0 || h > cmax[0]) continue;
+        for (int dm = (D == 3 ? -1 : 0); dm <= (D == 3 ? 1 : 0); ++dm) {
+            const int64_t mm = cm + dm;
+            if (D == 3 && (mm < 0 || mm > cmax[1])) continue;
+            const uint64_t row = (((uint64_t)h << bm) | (uint64_t)mm) << bl;
+            f((int64_t)first(row | (uint64_t)l0), (int64_t)first((row | (uint64_t)l1) + 1));
+        }
+    }
+}
+
+// The cells of the rows `rows` of xyz on the grid of ror_key_bits, as sorted (key, position in rows) pairs
+template <int D>
+std::vector<std::pair<uint64_t, int64_t>> host_keys(const double* xyz, const int64_t* rows, int64_t m, double leaf,
+                                                    const double (&cmin)[3], const int32_t (&bits)[3]) {
+    std::vector<std::pair<uint64_t, int64_t>> ks((size_t)m);
+    for (int64_t s = 0; s < m; ++s) {
+        uint64_t key = 0;
+        for (int a = 0; a < D; ++a)
+            key = (key << bits[a]) | (uint64_t)(int64_t)(std::floor(xyz[(rows ? rows[s] : s) * D + a] / leaf) - cmin[a]);
+        ks[s] = {key, s};
+    }
+    std::sort(ks.begin(), ks.end());
+    return ks;
+}
 
 // The host yardstick: the device's algorithm as plain loops -- keys of the same grid, one sort, and per point the
 // same clipped key runs searched in the sorted keys.
@@ -503,37 +543,15 @@ void filter_host(const double* xyz, int64_t N, const gicp_filter& f, double* out
         int32_t bits[3];
         int64_t cmax[3];
         ror_key_bits(D, mn, mx, f.radius, leaf, cmin, bits, cmax);
-        std::vector<std::pair<uint64_t, int64_t>> ks((size_t)m);   // (key, survivor)
-        for (int64_t s = 0; s < m; ++s) {
-            uint64_t key = 0;
-            for (int a = 0; a < D; ++a)
-                key = (key << bits[a]) | (uint64_t)(int64_t)(std::floor(xyz[rows[s] * D + a] / leaf) - cmin[a]);
-            ks[s] = {key, s};
-        }
-        std::sort(ks.begin(), ks.end());
+        const std::vector<std::pair<uint64_t, int64_t>> ks = host_keys<D>(xyz, rows.data(), m, leaf, cmin, bits);   // (key, survivor)
         const double r2 = f.radius * f.radius;
-        const int bl = bits[D - 1], bm = D == 3 ? bits[1] : 0;
-        auto first = [&](uint64_t k) { return std::lower_bound(ks.begin(), ks.end(), std::make_pair(k, (int64_t)-1)) - ks.begin(); };
         for (int64_t j = 0; j < m; ++j) {
-            const uint64_t key = ks[j].first;
             const double* p = xyz + rows[ks[j].second] * D;
-            const int64_t cl = (int64_t)(key & ((1ull << bl) - 1ull));
-            const int64_t cm = D == 3 ? (int64_t)((key >> bl) & ((1ull << bm) - 1ull)) : 0;
-            const int64_t ch = (int64_t)(key >> (bl + bm));
-            const int64_t l0 = cl > 0 ? cl - 1 : 0, l1 = cl < cmax[D - 1] ? cl + 1 : cl;
             int32_t count = 0;
-            for (int dh = -1; dh <= 1; ++dh) {
-                const int64_t h = ch + dh;
-                if (h < 0 || h > cmax[0]) continue;
-                for (int dm = (D == 3 ? -1 : 0); dm <= (D == 3 ? 1 : 0); ++dm) {
-                    const int64_t mm = cm + dm;
-                    if (D == 3 && (mm < 0 || mm > cmax[1])) continue;
-                    const uint64_t row = (((uint64_t)h << bm) | (uint64_t)mm) << bl;
-                    const int64_t b = first(row | (uint64_t)l0), e = first((row | (uint64_t)l1) + 1);
-                    for (int64_t t = b; t < e; ++t)
-                        if (t != j && ror_near(filter_d2<D>(p, xyz + rows[ks[t].second] * D), r2)) ++count;
-                }
-            }
+            host_runs<D>(ks, ks[j].first, bits, cmax, [&](int64_t b, int64_t e) {
+                for (int64_t t = b; t < e; ++t)
+                    if (t != j && ror_near(filter_d2<D>(p, xyz + rows[ks[t].second] * D), r2)) ++count;
+            });
             const int64_t s = ks[j].second;
             keep[s] = count >= f.min_neighbors;
             if (out_count) out_count[rows[s]] = count;
@@ -733,6 +751,107 @@ void sor_points_host(const double* xyz, int64_t N, int dim, const gicp_sor* s, d
     check_sor_args(xyz, N, dim, s, M_out, mn, mx);   // (a refused call writes nothing, *M_out included)
     if (dim == 3) sor_host<3>(xyz, N, *s, out_xyz, out_index, out_mean, out_stats, M_out);
     else sor_host<2>(xyz, N, *s, out_xyz, out_index, out_mean, out_stats, M_out);
+}
+
+// ---- Euclidean cluster extraction (gicp_cluster.h) ----
+
+// what gicp_set_cluster, gicp_cluster_points and gicp_cluster_points_host refuse alike of the setting
+void check_cluster(const gicp_cluster& c) {
+    if (!(std::isfinite(c.radius) && c.radius > 0.0)) throw Fail{GICP_E_INVALID, "cluster: radius must be finite and > 0"};
+    if (c.min_size < 1) throw Fail{GICP_E_INVALID, "cluster: min_size must be >= 1"};
+    if (c.max_size < 0 || (c.max_size > 0 && c.max_size < c.min_size)) {
+        char b[160];
+        std::snprintf(b, sizeof b, "cluster: max_size %d must be 0 (no upper limit) or at least min_size %d", (int)c.max_size,
+                      (int)c.min_size);
+        throw Fail{GICP_E_INVALID, b};
+    }
+}
+
+// the argument checks of both one-shot entry points, the finiteness test and the bounds it yields
+void check_cluster_args(const double* xyz, int64_t N, int dim, const gicp_cluster* c, double (&mn)[3], double (&mx)[3]) {
+    if (!xyz || (dim != 2 && dim != 3)) throw Fail{GICP_E_INVALID, "cluster: the cloud must be an N x 2 or N x 3 array"};
+    if (N < 1 || N > (int64_t)0x7FFFFFFF - 64) throw Fail{GICP_E_INVALID, "cluster: the cloud must hold 1 .. 2^31 - 65 rows"};
+    if (!c) throw Fail{GICP_E_INVALID, "cluster: the setting must not be NULL"};
+    check_cluster(*c);
+    try {
+        scan_bounds(xyz, N, dim, mn, mx);
+    } catch (const Fail& f) {
+        throw Fail{f.code, "cluster: " + f.msg};
+    }
+}
+
+// what a stage of m rows in `clusters` clusters refuses of its own result: no row kept
+void check_cluster_result(int64_t kept, int64_t m, int64_t clusters, const gicp_cluster& c) {
+    if (kept > 0) return;
+    char b[224];
+    std::snprintf(b, sizeof b, "cluster: none of the %lld clusters of the %lld points has a size in [min_size %d, max_size %d] (radius %g)",
+                  (long long)clusters, (long long)m, (int)c.min_size, (int)c.max_size, c.radius);
+    throw Fail{GICP_E_INVALID, b};
+}
+
+namespace {
+// The host yardstick: a union-find over the pairs the device's grid proposes (the same keys, the same clipped runs)
+// and the same predicate decides.  Plain, not fast.
+template <int D>
+void cluster_host(const double* xyz, int64_t N, const gicp_cluster& c, const double (&mn)[3], const double (&mx)[3], int32_t* labels,
+                  int32_t* sizes, int64_t* n_clusters, double* out_xyz, int64_t* out_index, int64_t* M_out) {
+    double leaf, cmin[3];
+    int32_t bits[3];
+    int64_t cmax[3];
+    ror_key_bits(D, mn, mx, c.radius, leaf, cmin, bits, cmax, "cluster");
+    const std::vector<std::pair<uint64_t, int64_t>> ks = host_keys<D>(xyz, nullptr, N, leaf, cmin, bits);
+    std::vector<int32_t> parent((size_t)N);
+    for (int64_t i = 0; i < N; ++i) parent[i] = (int32_t)i;
+    auto find = [&](int32_t x) {
+        while (parent[x] != x) x = parent[x] = parent[parent[x]];
+        return x;
+    };
+    const double r2 = c.radius * c.radius;
+    for (int64_t j = 0; j < N; ++j) {
+        const int64_t i = ks[j].second;
+        host_runs<D>(ks, ks[j].first, bits, cmax, [&](int64_t b, int64_t e) {
+            for (int64_t t = b > j ? b : j + 1; t < e; ++t) {
+                if (!ror_near(filter_d2<D>(xyz + i * D, xyz + ks[t].second * D), r2)) continue;
+                const int32_t ra = find((int32_t)i), rb = find((int32_t)ks[t].second);
+                if (ra != rb) parent[ra > rb ? ra : rb] = ra > rb ? rb : ra;   // the larger root below the smaller
+            }
+        });
+    }
+    // a root is its cluster's smallest row: numbering the roots as they come numbers the clusters
+    std::vector<int32_t> lab((size_t)N), sz;
+    for (int64_t i = 0; i < N; ++i) {
+        const int32_t r = find((int32_t)i);
+        if (r == i) {
+            lab[i] = (int32_t)sz.size();
+            sz.push_back(0);
+        }
+        ++sz[lab[i] = lab[r]];
+    }
+    int64_t M = 0;
+    for (int64_t i = 0; i < N; ++i) M += cluster_keeps(sz[lab[i]], c.min_size, c.max_size) ? 1 : 0;
+    check_cluster_result(M, N, (int64_t)sz.size(), c);   // (a refused call writes nothing)
+    M = 0;
+    for (int64_t i = 0; i < N; ++i) {
+        if (labels) labels[i] = lab[i];
+        if (!cluster_keeps(sz[lab[i]], c.min_size, c.max_size)) continue;
+        if (out_xyz)
+            for (int a = 0; a < D; ++a) out_xyz[M * D + a] = xyz[i * D + a];
+        if (out_index) out_index[M] = i;
+        ++M;
+    }
+    if (sizes)
+        for (size_t k = 0; k < sz.size(); ++k) sizes[k] = sz[k];
+    if (n_clusters) *n_clusters = (int64_t)sz.size();
+    if (M_out) *M_out = M;
+}
+}  // namespace
+
+void cluster_points_host(const double* xyz, int64_t N, int dim, const gicp_cluster* c, int32_t* labels, int32_t* sizes,
+                         int64_t* n_clusters, double* out_xyz, int64_t* out_index, int64_t* M_out) {
+    double mn[3], mx[3];
+    check_cluster_args(xyz, N, dim, c, mn, mx);
+    if (dim == 3) cluster_host<3>(xyz, N, *c, mn, mx, labels, sizes, n_clusters, out_xyz, out_index, M_out);
+    else cluster_host<2>(xyz, N, *c, mn, mx, labels, sizes, n_clusters, out_xyz, out_index, M_out);
 }
 
 // ---- what every entry point checks the same way ----
@@ -986,6 +1105,23 @@ int gicp_sor_points_host(const double* xyz, int64_t N, int dim, const gicp_sor* 
         const int rc = gicp::current_failure(msg);
         try {
             t_host_err = "gicp_sor_points_host: " + msg;
+        } catch (...) {
+        }
+        return rc == GICP_E_NOMEM ? GICP_E_INVALID : rc;
+    }
+}
+
+// ... and of Euclidean cluster extraction
+int gicp_cluster_points_host(const double* xyz, int64_t N, int dim, const gicp_cluster* c, int32_t* labels, int32_t* sizes,
+                             int64_t* n_clusters, double* out_xyz, int64_t* out_index, int64_t* M_out) {
+    try {
+        gicp::cluster_points_host(xyz, N, dim, c, labels, sizes, n_clusters, out_xyz, out_index, M_out);
+        return GICP_OK;
+    } catch (...) {
+        std::string msg;
+        const int rc = gicp::current_failure(msg);
+        try {
+            t_host_err = "gicp_cluster_points_host: " + msg;
         } catch (...) {
         }
         return rc == GICP_E_NOMEM ? GICP_E_INVALID : rc;

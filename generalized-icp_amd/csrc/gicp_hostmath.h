@@ -114,7 +114,7 @@ void check_filter(const gicp_filter& f);
 bool filter_crops(const gicp_filter& f);
 [[noreturn]] void fail_filter_empty(int stage, int64_t n, const gicp_filter& f);
 int ror_key_bits(int dim, const double (&mn)[3], const double (&mx)[3], double radius, double& leaf, double (&cmin)[3],
-                 int32_t (&bits)[3], int64_t (&cmax)[3]);
+                 int32_t (&bits)[3], int64_t (&cmax)[3], const char* stage = "filter");
 void check_filter_args(const double* xyz, int64_t N, int dim, const gicp_filter* f, const double* out_xyz, const int64_t* M_out);
 void filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz, int64_t* out_index,
                         int32_t* out_count, int64_t* M_out);
@@ -132,6 +132,13 @@ void check_sor_extent(int dim, const double (&mn)[3], const double (&mx)[3]);
 void check_sor_result(double t_mean, int64_t kept, int64_t m, const gicp_sor& s);
 void sor_points_host(const double* xyz, int64_t N, int dim, const gicp_sor* s, double* out_xyz, int64_t* out_index,
                      double* out_mean, double* out_stats, int64_t* M_out);
+
+// Euclidean cluster extraction: the setting's checks, what a stage refuses, the host yardstick
+void check_cluster(const gicp_cluster& c);
+void check_cluster_args(const double* xyz, int64_t N, int dim, const gicp_cluster* c, double (&mn)[3], double (&mx)[3]);
+void check_cluster_result(int64_t kept, int64_t m, int64_t clusters, const gicp_cluster& c);
+void cluster_points_host(const double* xyz, int64_t N, int dim, const gicp_cluster* c, int32_t* labels, int32_t* sizes,
+                         int64_t* n_clusters, double* out_xyz, int64_t* out_index, int64_t* M_out);
 
 // registration report: information matrix of a pass's statistics, symmetric eigensolver
 void information(int dim, const double* stats, const double* T, double* H, double* b);

@@ -24,7 +24,7 @@ from ._lib import Debug, Params, Report, ReportSpec, Result, Trace, check, dptr
 __all__ = ["gicp", "apply_transformation", "Engine", "RotatedCovariances", "expand_stats", "stats_size",
            "default_params", "last_result", "voxel_downsample", "filter_points", "filter_points_host", "deskew", "deskew_host", "motion_twist", "information",
            "sym_eig", "align_batch", "multistart", "batch_max_points", "pick_start", "knn", "knn_host", "knn_max_k", "sor_points", "sor_points_host",
-           "sor_max_k"]
+           "sor_max_k", "cluster_points", "cluster_points_host"]
 
 
 def stats_size(dim):
@@ -133,6 +133,7 @@ class Engine:
         self.voxel = (0.0, 1)      # (voxel_size, min_points) of set_voxel; size 0: no filter
         self.filter = _NO_FILTER   # the keywords of set_filter in force (all zero: no filter)
         self.sor = (0, 0.0)        # (k, std_ratio) of set_sor; k 0: off
+        self.cluster = (0.0, 1, 0)  # (radius, min_size, max_size) of set_cluster; radius 0: off
         self.map_dim = None        # dimension of the local voxel map (map_reset)
 
     def close(self):
@@ -298,7 +299,7 @@ class Engine:
 
     def _reduces(self):
         """A filter of the builds is in force (set_voxel, set_filter): a cloud then holds fewer rows than its input."""
-        return self.voxel[0] > 0 or _filter_on(self.filter) or self.sor[0] > 0
+        return self.voxel[0] > 0 or _filter_on(self.filter) or self.sor[0] > 0 or self.cluster[0] > 0
 
     def set_sor(self, k, std_ratio=1.0):
         """Statistical outlier removal of every cloud set or staged from now on (gicp_set_sor), on the
@@ -317,6 +318,26 @@ class Engine:
         a = self._cloud(points)
         return _sor_call(lambda *args: check(self._lib.gicp_sor_points(self._ctx, *args), self._ctx, "gicp_sor_points"),
                          a, k, std_ratio, return_index, return_mean, return_stats)
+
+    def set_cluster(self, radius, min_size=1, max_size=0):
+        """Euclidean cluster extraction of every cloud set or staged from now on (gicp_set_cluster), on
+        the device, after statistical outlier removal and before the voxel filter: the rows within `radius` of each
+        other form the edges of a graph, its connected components are the clusters, and the rows of the clusters
+        with min_size <= size (and size <= max_size unless max_size is 0) are kept (gicp.cluster_points has the
+        definition).  radius None or 0 turns it off.  With it, every per-point output of this engine refers to the
+        rows of the FILTERED clouds, which points() returns: the input's rows that survive, in their order.
+        Engine.cluster holds the setting as (radius, min_size, max_size)."""
+        radius = 0.0 if radius is None else float(radius)
+        c = _lib.Cluster(radius, int(min_size) if radius else 1, int(max_size) if radius else 0)
+        check(self._lib.gicp_set_cluster(self._ctx, C.byref(c)), self._ctx, "gicp_set_cluster")
+        self.cluster = (c.radius, c.min_size, c.max_size)
+
+    def cluster_points(self, points, radius, min_size=1, max_size=0, return_index=False, return_labels=False, return_sizes=False):
+        """gicp.cluster_points on this engine's GPU (gicp_cluster_points); the engine's clouds and settings are
+        untouched."""
+        a = self._cloud(points)
+        return _cluster_call(lambda *args: check(self._lib.gicp_cluster_points(self._ctx, *args), self._ctx, "gicp_cluster_points"),
+                             a, radius, min_size, max_size, return_index, return_labels, return_sizes)
 
     def set_filter(self, center=None, min_range=0.0, max_range=0.0, radius=0.0, min_neighbors=1):
         """Input filters of every cloud set or staged from now on (gicp_set_filter), on the device,
@@ -1083,6 +1104,58 @@ def sor_points_host(points, k, std_ratio=1.0, return_index=False, return_mean=Fa
     return _sor_call(call, a, k, std_ratio, return_index, return_mean, return_stats)
 
 
+def _cluster_call(call, a, radius, min_size, max_size, return_index, return_labels, return_sizes):
+    """One one-shot cluster-extraction call (device or host) on the cloud `a`."""
+    c = _lib.Cluster(float(radius), int(min_size), int(max_size))
+    n = a.shape[0]
+    out = np.empty_like(a)
+    idx = np.empty(n, dtype=np.int64) if return_index else None
+    labels = np.empty(n, dtype=np.int32) if return_labels else None
+    sizes = np.empty(n, dtype=np.int32) if return_sizes else None
+    m, nc = C.c_int64(), C.c_int64()
+    i32 = C.POINTER(C.c_int32)
+    call(dptr(a), n, a.shape[1], C.byref(c), labels.ctypes.data_as(i32) if return_labels else None,
+         sizes.ctypes.data_as(i32) if return_sizes else None, C.byref(nc), dptr(out),
+         idx.ctypes.data_as(C.POINTER(C.c_int64)) if return_index else None, C.byref(m))
+    res = (out[:m.value].copy(),)
+    if return_index:
+        res += (idx[:m.value].copy(),)
+    if return_labels:
+        res += (labels,)
+    if return_sizes:
+        res += (sizes[:nc.value].copy(),)
+    return res[0] if len(res) == 1 else res
+
+
+def cluster_points(points, radius, min_size=1, max_size=0, return_index=False, return_labels=False, return_sizes=False,
+                   device=0):
+    """Euclidean cluster extraction on the GPU (gicp_cluster_points): rows i != j of `points` (N x 2 or
+    N x 3, N >= 1) are adjacent iff d2 = ((dx*dx + dy*dy) + dz*dz) <= radius*radius in fp64, every operation rounded on
+    its own and the bound inclusive (coincident rows are adjacent); the clusters are the connected components,
+    numbered 0 .. C - 1 in ascending order of their smallest row; a cluster is kept iff min_size <= size and
+    (max_size == 0 or size <= max_size).  Defined to the bit (include/gicp_hip.h): the host function and a NumPy /
+    SciPy restatement give the same arrays.  Returns the rows of the kept clusters in their order; with return_index
+    also their int64 rows in `points`; with return_labels also, per INPUT row, the int32 number of its cluster (kept
+    or not); with return_sizes also the int32 sizes of the C clusters.  Deterministic.  Raises ValueError for a radius
+    that is not finite and > 0, min_size < 1, max_size below min_size (0: no limit), non-finite input, a cloud spanning
+    more than 2^21 (3-D) / 2^31 (2-D) cells of edge radius on an axis, and a decision that keeps no row."""
+    return _engine(int(device)).cluster_points(points, radius, min_size, max_size, return_index, return_labels, return_sizes)
+
+
+def cluster_points_host(points, radius, min_size=1, max_size=0, return_index=False, return_labels=False, return_sizes=False):
+    """`cluster_points` computed on the host by a union-find over the same grid and predicate
+    (gicp_cluster_points_host; no GPU needed): the CPU yardstick."""
+    a = Engine._cloud(points)
+    lib = _lib.load()
+
+    def call(*args):
+        rc = lib.gicp_cluster_points_host(*args)
+        if rc != _lib.GICP_OK:   # (host only: the message is the thread's, there is no context)
+            raise ValueError(lib.gicp_last_host_error().decode())
+
+    return _cluster_call(call, a, radius, min_size, max_size, return_index, return_labels, return_sizes)
+
+
 def _knn_array(a, name):
     a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
     if a.ndim != 2:
@@ -1258,7 +1331,8 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
          devices=None, verbose=True, T0=None, method="plane_to_plane", transformation_epsilon=0.0,
          rotation_epsilon=0.0, euclidean_fitness_epsilon=0.0, mse_relative_epsilon=0.0, voxel_size=None,
          voxel_min_points=1, robust_kernel=None, robust_scale=None, min_range=None, max_range=None, outlier_radius=None,
-         outlier_min_neighbors=1, filter_center=None, sor_k=None, sor_std_ratio=1.0):
+         outlier_min_neighbors=1, filter_center=None, sor_k=None, sor_std_ratio=1.0, cluster_radius=None,
+         cluster_min_size=1, cluster_max_size=0):
     """Drop-in for gicp.py:78 — returns the same 7-tuple (gicp.py:174):
 
     (T, all_transformations, initial_source_cov_matrices, target_cov_matrices,
@@ -1306,6 +1380,10 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
     sor_k / sor_std_ratio: sor_k None (default) registers the clouds as given.  Otherwise both clouds pass
       statistical outlier removal on the device (Engine.set_sor) after the input filters and before the voxel
       filter, and every per-point member of the 7-tuple refers to the FILTERED clouds.
+    cluster_radius / cluster_min_size / cluster_max_size: cluster_radius None (default) registers the clouds as
+      given.  Otherwise both clouds pass Euclidean cluster extraction on the device (Engine.set_cluster) after
+      statistical outlier removal and before the voxel filter: only the rows of the clusters whose size lies in
+      the limits stay, and every per-point member of the 7-tuple refers to the FILTERED clouds.
     robust_kernel / robust_scale: None (default) is plain least squares.  'huber', 'cauchy',
       'geman_mcclure' ('gm') or 'tukey' (or the GICP_ROBUST_* code) weights every accepted
       correspondence of a pass by the kernel's w(s / robust_scale), s = sqrt(r^T W r) the whitened residual
@@ -1355,13 +1433,14 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
     filt = None
     if not (min_range is None and max_range is None and outlier_radius is None):
         filt = _filter_kw(filter_center, min_range, max_range, outlier_radius, outlier_min_neighbors)
-    if voxel_size is None and filt is None and sor_k is None:
+    if voxel_size is None and filt is None and sor_k is None and cluster_radius is None:
         _run_ranks(engines, build)
         eng = engines[0]
     else:   # the engines are shared between calls: the settings last for this call's builds only
         prev_voxel = [e.voxel for e in engines]
         prev_filter = [e.filter for e in engines]
         prev_sor = [e.sor for e in engines]
+        prev_cluster = [e.cluster for e in engines]
         try:
             for e in engines:
                 if voxel_size is not None:
@@ -1370,16 +1449,19 @@ def gicp(source_points, target_points, max_iterations=100, tolerance=1e-6, max_d
                     e.set_filter(**filt)
                 if sor_k is not None:
                     e.set_sor(sor_k, sor_std_ratio)
+                if cluster_radius is not None:
+                    e.set_cluster(cluster_radius, cluster_min_size, cluster_max_size)
             _run_ranks(engines, build)
             eng = engines[0]
             # the host side of the loops (highest-weight points, the faithful mode's moved source) works on
             # the clouds the engine registers
             src, tgt = eng.points("source"), eng.points("target")
         finally:
-            for e, v, f, s in zip(engines, prev_voxel, prev_filter, prev_sor):
+            for e, v, f, s, cl in zip(engines, prev_voxel, prev_filter, prev_sor, prev_cluster):
                 e.set_voxel(*v)
                 e.set_filter(**f)
                 e.set_sor(*s)
+                e.set_cluster(*cl)
     target_cov = eng.covariances("target")
     init_src_cov = eng.covariances("source")
     for e in engines[1:]:   # each device computed its own shard's source covariances (NaN elsewhere)

@@ -139,6 +139,15 @@ class Sor(C.Structure):
     ]
 
 
+class Cluster(C.Structure):
+    """gicp_cluster (include/gicp_hip.h): Euclidean cluster extraction of a cloud; radius = 0: off."""
+    _fields_ = [
+        ("radius", C.c_double),
+        ("min_size", C.c_int32),
+        ("max_size", C.c_int32),
+    ]
+
+
 class BatchProblem(C.Structure):
     """gicp_batch_problem (include/gicp_hip.h): one registration of a batch."""
     _fields_ = [
@@ -297,6 +306,13 @@ SIGNATURES = {
     "gicp_sor_points_host": (C.c_int, [_DP, C.c_int64, C.c_int, C.POINTER(Sor), _DP, C.POINTER(C.c_int64), _DP, _DP,
                                        C.POINTER(C.c_int64)]),
     "gicp_set_sor": (C.c_int, [_VP, C.POINTER(Sor)]),
+    "gicp_cluster_points": (C.c_int, [_VP, _DP, C.c_int64, C.c_int, C.POINTER(Cluster), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int64), _DP, C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int64)]),
+    "gicp_cluster_points_host": (C.c_int, [_DP, C.c_int64, C.c_int, C.POINTER(Cluster), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), C.POINTER(C.c_int64), _DP, C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64)]),
+    "gicp_set_cluster": (C.c_int, [_VP, C.POINTER(Cluster)]),
 }
 
 # gicp_allreduce_fn: int (*)(double* buf, int n, void* user)
@@ -309,12 +325,12 @@ HASH_SRCS = ("csrc/gicp_index.hip", "csrc/gicp_cov.hip", "csrc/gicp_corr.hip", "
              "csrc/gicp_capi.cpp", "csrc/gicp_solver.cpp", "csrc/gicp_cg.cpp", "csrc/gicp_hostmath.cpp",
              "csrc/gicp_build.cpp", "csrc/gicp_align.cpp", "csrc/gicp_exchange.cpp", "csrc/gicp_voxel.hip",
              "csrc/gicp_sweep.hip", "csrc/gicp_eval.hip", "csrc/gicp_filter.hip", "csrc/gicp_batch.hip", "csrc/gicp_batch.cpp",
-             "csrc/gicp_knn.hip", "csrc/gicp_sor.hip",
+             "csrc/gicp_knn.hip", "csrc/gicp_sor.hip", "csrc/gicp_cluster.hip",
              "csrc/gicp_internal.h", "csrc/gicp_mem.h",
              "csrc/gicp_sweep.h", "csrc/gicp_filter.h", "csrc/gicp_cov_dev.h", "csrc/gicp_solver.h", "csrc/gicp_solve_dev.h", "csrc/gicp_hostmath.h", "csrc/gicp_host.h",
              "../include/gicp_hip.h",
              "csrc/gicp_wave_dev.h", "csrc/gicp_search_dev.h", "csrc/gicp_stats_dev.h", "csrc/gicp_bounds_dev.h",
-             "csrc/gicp_sor.h")
+             "csrc/gicp_sor.h", "csrc/gicp_cluster.h", "csrc/gicp_runs_dev.h")
 
 
 def source_hash():

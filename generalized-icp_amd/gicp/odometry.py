@@ -40,7 +40,8 @@ class Odometry:
     def __init__(self, dim=3, params=None, device=0, composition="se3", init="constant_velocity", borrow=False,
                  voxel_size=None, voxel_min_points=1, map_voxel_size=None, map_range=None, map_min_points=1,
                  deskew=False, deskew_ref=0.5, report=None, min_range=None, max_range=None, outlier_radius=None,
-                 outlier_min_neighbors=1, sor_k=None, sor_std_ratio=1.0, **kw):
+                 outlier_min_neighbors=1, sor_k=None, sor_std_ratio=1.0, cluster_radius=None, cluster_min_size=1,
+                 cluster_max_size=0, **kw):
         if composition not in ("se3", "reference"):
             raise ValueError("composition must be 'se3' or 'reference'")
         if init not in ("identity", "constant_velocity"):
@@ -77,6 +78,10 @@ class Odometry:
         # after those filters and before the voxel filter
         if sor_k is not None:
             self.eng.set_sor(sor_k, sor_std_ratio)
+        # cluster_radius / cluster_min_size / cluster_max_size: every scan then passes Euclidean cluster extraction on
+        # the device (Engine.set_cluster), after statistical outlier removal and before the voxel filter
+        if cluster_radius is not None:
+            self.eng.set_cluster(cluster_radius, cluster_min_size, cluster_max_size)
         self.composition = composition
         self.init = init
         # borrow=True: staged scans are read by the library in place (GICP_STAGE_BORROW, no copy on this

@@ -165,7 +165,8 @@ int gicp_version(void);                          /* 100 * major + minor; 101: gi
                                                     exact k-nearest-neighbour queries (gicp_knn, gicp_knn_points,
                                                     gicp_knn_host, gicp_knn_max_k); 107: statistical outlier
                                                     removal (gicp_sor, gicp_sor_points[_host], gicp_set_sor,
-                                                    gicp_sor_max_k) */
+                                                    gicp_sor_max_k); 108: Euclidean cluster extraction
+                                                    (gicp_cluster, gicp_cluster_points[_host], gicp_set_cluster) */
 int gicp_stats_size(int dim);                    /* 26 (dim 2) or 74 (dim 3) */
 void gicp_default_params(int dim, gicp_params* out);
 const char* gicp_strerror(int code);
@@ -211,10 +212,11 @@ int gicp_peer_close(gicp_ctx* ctx);   /* back to no exchange (RCCL / hook as set
 /* Build provenance of this library: "src=<first 16 hex of sha256 over the sources>;git=<rev>;built=<date
  * time>;arch=gfx950".  The source hash covers csrc/{gicp_index.hip, gicp_cov.hip, gicp_corr.hip, gicp_extras.hip,
  * gicp_capi.cpp, gicp_solver.cpp, gicp_cg.cpp, gicp_hostmath.cpp, gicp_build.cpp, gicp_align.cpp, gicp_exchange.cpp,
- * gicp_voxel.hip, gicp_sweep.hip, gicp_eval.hip, gicp_filter.hip, gicp_batch.hip, gicp_batch.cpp, gicp_knn.hip, gicp_sor.hip, gicp_internal.h,
+ * gicp_voxel.hip, gicp_sweep.hip, gicp_eval.hip, gicp_filter.hip, gicp_batch.hip, gicp_batch.cpp, gicp_knn.hip, gicp_sor.hip,
+ * gicp_cluster.hip, gicp_internal.h,
  * gicp_mem.h, gicp_sweep.h, gicp_filter.h, gicp_cov_dev.h, gicp_solver.h, gicp_solve_dev.h, gicp_hostmath.h,
  * gicp_host.h}, include/gicp_hip.h and csrc/{gicp_wave_dev.h, gicp_search_dev.h, gicp_stats_dev.h,
- * gicp_bounds_dev.h, gicp_sor.h}, concatenated in that order (the Makefile's SRCS, then its HEADERS), so
+ * gicp_bounds_dev.h, gicp_sor.h, gicp_cluster.h, gicp_runs_dev.h}, concatenated in that order (the Makefile's SRCS, then its HEADERS), so
  * a caller can prove the loaded library was compiled from the sources beside it. */
 const char* gicp_build_info(void);
 
@@ -499,7 +501,7 @@ int gicp_filter_points(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, con
                        int64_t* out_index, int32_t* out_count, int64_t* M_out);
 int gicp_filter_points_host(const double* xyz, int64_t N, int dim, const gicp_filter* f, double* out_xyz,
                             int64_t* out_index, int32_t* out_count, int64_t* M_out);
-const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host, gicp_knn_host or gicp_sor_points_host, or refused gicp_batch_align ("" if none) */
+const char* gicp_last_host_error(void);   /* of this thread's last failed gicp_filter_points_host, gicp_knn_host, gicp_sor_points_host or gicp_cluster_points_host, or refused gicp_batch_align ("" if none) */
 int gicp_set_filter(gicp_ctx* ctx, const gicp_filter* f);
 
 /* ---- local voxel map ----------------------------------------------------------------
@@ -764,6 +766,60 @@ int gicp_sor_points(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, const 
 int gicp_sor_points_host(const double* xyz, int64_t N, int dim, const gicp_sor* s, double* out_xyz, int64_t* out_index,
                          double* out_mean, double* out_stats, int64_t* M_out);
 int gicp_set_sor(gicp_ctx* ctx, const gicp_sor* s);
+
+/* ---- Euclidean cluster extraction ------------------------------------------------------
+ * The connected components of the graph "rows within `radius` of each other" (PCL's EuclideanClusterExtraction,
+ * Open3D's cluster_dbscan with min_points 1), and the rows of the clusters whose size lies in given limits: what
+ * removes a clump of returns that are each other's neighbours, which both outlier filters above keep, and what finds
+ * objects.  Defined to the bit.
+ * Input: N >= 1 rows, finite, dim 2 or 3, and a gicp_cluster.
+ *   1. EDGES.  i ~ j (i != j) iff d2(p_i, p_j) <= radius * radius: d2 the expression of the input filters above, fp64
+ *      with every product and sum rounded on its own (no FMA), the squared radius one rounded product, the bound
+ *      inclusive.  Coincident rows are adjacent.  Hence a row is a singleton exactly when radius outlier removal's
+ *      count_i at the same radius is 0.
+ *   2. CLUSTERS.  The connected components of that graph.  Only the set partition is defined; nothing depends on
+ *      the order in which anything is traversed.
+ *   3. NUMBERING.  Clusters are numbered 0 .. C - 1 in ascending order of their smallest original row.  labels[i]
+ *      (int32, per input row) is the number of row i's cluster, sizes[c] (int32) the row count of cluster c.  Every
+ *      row has a label, whether its cluster is kept or not.
+ *   4. DECISION.  A cluster is kept iff min_size <= size and (max_size == 0 or size <= max_size).  Kept rows keep
+ *      their relative order.
+ *   5. DETERMINISM.  Integer atomics only, no floating-point atomics: the output is bit-identical from call to
+ *      call, context to context, and to the host function's.
+ * GICP_E_INVALID, with the stage named in the message ("cluster: ..."), for: a radius that is not finite or is <= 0
+ * (gicp_set_cluster takes 0 as off); min_size < 1; max_size < 0 or 0 < max_size < min_size; N < 1 or N >= 2^31 - 64;
+ * non-finite input; a cloud spanning more than 2^21 (3-D) or 2^31 (2-D) cells of edge `radius` on an axis (the
+ * message names the axis), or lying beyond 2^35 such cells from the origin -- the limits of radius outlier removal,
+ * whose grid this is; a decision that keeps no row.  A refused call writes nothing.
+ *
+ * One-shot, host in, host out (gicp_cluster_points): labels [N], sizes [N] (the first C entries are written; N is the
+ * worst case), n_clusters, out_xyz [N][dim], out_index [N] and M_out are caller-allocated and any of them may be
+ * NULL; *M_out receives the number of rows kept (they come first in out_xyz and out_index; out_index: the original
+ * row of each, ascending).  The context's clouds and settings are untouched.  gicp_cluster_points_host is host only
+ * (no HIP call, no context): a union-find over the pairs the same grid proposes, the CPU yardstick; its message is
+ * gicp_last_host_error()'s.  The device makes ONE lock-free pass over the edges whatever the shape of the components:
+ * there are no rounds to count.
+ *
+ * Context setting (gicp_set_cluster; NULL or radius = 0: off, the default): every later cloud build runs
+ *   upload -> de-skew -> crop -> radius outlier removal -> statistical outlier removal -> CLUSTER EXTRACTION ->
+ *   voxel filter -> index
+ * on the device.  The stage works on the survivors of the stages before it (N above is their number, "original row"
+ * theirs), keeps the rows of the kept clusters and hands the next stage these rows and their exact bounds on the
+ * device; it costs one stream synchronisation, in which only result words return to the host.  A staged build uses
+ * the setting in force when it was staged, on its own stream and scratch; GICP_STAGE_BORROW still reads the
+ * caller's frame in place.  With a sharded source every rank filters the whole cloud.  A failure after the build
+ * began leaves that cloud NOT SET.  With the setting off a build is what it was without this section. */
+typedef struct gicp_cluster {
+    double radius;      /* finite, > 0; 0: off (gicp_set_cluster only) */
+    int32_t min_size;   /* >= 1 */
+    int32_t max_size;   /* 0: no upper limit, else >= min_size */
+} gicp_cluster;
+int gicp_cluster_points(gicp_ctx* ctx, const double* xyz, int64_t N, int dim, const gicp_cluster* c,
+                        int32_t* labels /* [N] */, int32_t* sizes /* [N] worst case */, int64_t* n_clusters,
+                        double* out_xyz /* [N][dim] */, int64_t* out_index /* [N] */, int64_t* M_out);
+int gicp_cluster_points_host(const double* xyz, int64_t N, int dim, const gicp_cluster* c, int32_t* labels, int32_t* sizes,
+                             int64_t* n_clusters, double* out_xyz, int64_t* out_index, int64_t* M_out);
+int gicp_set_cluster(gicp_ctx* ctx, const gicp_cluster* c);
 
 #ifdef __cplusplus
 }
